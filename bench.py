@@ -11,6 +11,13 @@ One step = H2D-free synthetic batch already in HBM -> image tower || text tower 
 streams) -> fusion -> BCE -> backward -> (N>1: RCCL all-reduce of gradient buckets over
 xGMI) -> clip_grad_norm_(1.0) -> fused AdamW.  Run:  python bench.py [--gpus N --steps K
 --warmup W]; N>1 under torch.distributed.run (one process per GPU).
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds
+what takes work of its own: HIP events around the dominant kernel family's launches in the
+last timed steps (the `roofline` block, with the committed PMC figures), one more step on an
+idle device (`host_ms_one_step_idle_device`) and the CPU oracle's `cpu_baseline`
+(`--no-cpu-baseline` leaves that one out).  `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy (float32), for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -290,6 +297,7 @@ def make_step(img, txt, fus, opt, params, reducer, x, ids, mask, y, side, side_b
         with rng("mmdx/fusion_fwd"):
             logits = fus(z_img, z_txt)["disease_logits"]
             loss = mmdx.BCEWithLogitsLoss()(logits, y)
+        step.logits = logits.detach()
         if mk:
             mk("head_fwd", main)
         # = loss.backward(), with the text tower's backward queued before the image trunk's;
@@ -315,6 +323,7 @@ def make_step(img, txt, fus, opt, params, reducer, x, ids, mask, y, side, side_b
             mk("optimizer", torch.cuda.current_stream())
         return loss
     step.norm = None
+    step.logits = None   # the last step's disease logits (--dump-outputs)
     step.marks = None   # diagnostics: mark(name, stream) once each part is issued
     step.towers = towers   # (tools/host_profile.py profiles the text thread through it)
     return step
@@ -337,8 +346,43 @@ def capture_step(step):
         return out
     replay.graph = g
     replay.norm = step.norm
+    replay.logits = step.logits
     replay.towers = step.towers
     return replay
+
+
+DUMP_SAMPLE = 4096   # elements kept per parameter tensor (fixed, seeded positions)
+
+
+def dump_outputs(out_dir, loss, norm, logits, params):
+    """What the last timed step handed back, as float32 .npy files: the loss, the gradient
+    norm it clipped by, the fusion head's logits, and the same seeded DUMP_SAMPLE positions of
+    every parameter tensor after the update and of its gradient (whole tensors where they are
+    smaller; a parameter without a gradient contributes zeros): a few MB for every config.
+    Inputs, initial weights and dropout seeds are fixed, so two builds run with the same
+    arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(4321)
+    ps, gs = [], []
+    for p in params:
+        n = p.numel()
+        flat = p.detach().reshape(-1)
+        grad = p.grad.detach().reshape(-1) if p.grad is not None else torch.zeros_like(flat)
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(n, (DUMP_SAMPLE,), generator=g).to(p.device)
+            flat, grad = flat[idx], grad[idx]
+        ps.append(flat.float())
+        gs.append(grad.float())
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "grad_norm": torch.as_tensor(norm).detach().float().reshape(-1),
+        "logits": logits.detach().float(),
+        "params_sample": torch.cat(ps),
+        "grads_sample": torch.cat(gs),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def _cpu_model():
@@ -448,11 +492,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline block (HIP events around the dominant "
+                         "family's launches), the idle-device host cost and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-steps", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -578,10 +630,12 @@ def main():
     # LAST `ev_steps` timed steps (default K/10).  Bracketing every step costs ~0.75 ms/step
     # of event markers at C4 (316 records), which would bias `value`; the sampled steps are
     # ordinary steps of the timed loop, so the per-launch average is the timed region's.
-    timing = os.environ.get("MMDX_BENCH_EVENTS", "1") != "0"
+    # (--full only: a plain run brackets nothing)
+    timing = args.full and os.environ.get("MMDX_BENCH_EVENTS", "1") != "0"
     ev_steps = min(args.steps, max(1, int(os.environ.get("MMDX_BENCH_EVENT_STEPS",
                                                          max(1, args.steps // 10)))))
-    timer.reserve(400 * ev_steps)
+    if timing:
+        timer.reserve(400 * ev_steps)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -596,14 +650,18 @@ def main():
     if dp:
         dist.barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, step.norm, step.logits, params)
     # host cost of one step issued onto an idle device (no queue back-pressure)
-    was = timer.enabled
-    timer.enabled = False
-    t1 = time.perf_counter()
-    step()
-    host_one = time.perf_counter() - t1
-    torch.cuda.synchronize()
-    timer.enabled = was
+    host_one = None
+    if args.full:
+        was = timer.enabled
+        timer.enabled = False
+        t1 = time.perf_counter()
+        step()
+        host_one = time.perf_counter() - t1
+        torch.cuda.synchronize()
+        timer.enabled = was
     # MMDX_BENCH_TIMELINE=N (diagnostics): N more steps after the timed region with a HIP event
     # recorded when each part of the step has been issued, on the stream it runs on — when
     # each part ENDS on the device, in ms after the step's start (mean over the N steps): which
@@ -704,7 +762,7 @@ def main():
     alg_bytes = fam_bytes / max(1, conv_steps)
     alg_launches = max(1, n_conv // max(1, conv_steps))
     hbm_bound = byte_ms > flop_ms
-    traffic = load_traffic(args.config, B)
+    traffic = load_traffic(args.config, B) if args.full else None
     result = {
         "metric": "multimodal samples/sec (train fwd+bwd) at 1/2/4/8 MI355X; MFMA util %",
         "value": round(value, 2),
@@ -732,12 +790,12 @@ def main():
         "loss_scale": scaler.get_scale() if scaler is not None else None,
         "dp_bucket_dtype": ("bf16" if bdt is not None else "fp32") if dp else None,
         "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3),
-        "host_ms_one_step_idle_device": round(host_one * 1e3, 3),
+        "host_ms_one_step_idle_device": round(host_one * 1e3, 3) if args.full else None,
         **({"timeline_ms": timeline} if timeline else {}),
         "model_tflops": round(total_flops * samples / el / 1e12, 2),
         "mfma_util_pct_end_to_end": round(100 * total_flops * samples / el / 1e12 /
                                           (PEAK_BF16_TFLOPS * world), 2),
-        "mfma_util_pmc": load_mfma_util(args.config),
+        "mfma_util_pmc": load_mfma_util(args.config) if args.full else None,
         "amp": ({"loss_scaling": "mmdx.GradScaler (init 2^16, growth 2 per 2000 clean steps, "
                                  "backoff 0.5, device-side inf check, overflow skips AdamW)",
                  "clip_order": "reference (scaled): clip_grad_norm_(1.0) on the SCALED "
@@ -780,7 +838,9 @@ def main():
             "timed_steps_with_events": conv_steps,
         },
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:   # no launch was bracketed: the family figures would all read zero
+        del result["roofline"]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # C5's oracle (ViT-B/16 + BERT-base) takes seconds per CPU step: a shorter sample
         heavy = cfg["image"] == "vit_b_16"
         result["cpu_baseline"] = cpu_baseline(cfg, warmup=2 if heavy else 10,

@@ -1,5 +1,6 @@
 """bench.py's rank launcher (no GPU needed): `--gpus N` with no launcher around it starts N
-ranks under torch.distributed.run; a world that differs from --gpus is an error."""
+ranks under torch.distributed.run; a world that differs from --gpus is an error.  Also the
+--dump-outputs writer on CPU tensors: names, dtype, the fixed sample positions."""
 import os
 import subprocess
 import sys
@@ -44,3 +45,40 @@ def test_too_few_gpus_for_rccl_exits_nonzero():
 def test_gpus_must_be_positive():
     r = _run(["--gpus", "0"])
     assert r.returncode != 0 and "--gpus must be >= 1" in r.stderr
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_float32_arrays_at_fixed_positions(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(7)
+    big = torch.randn(3 * bench.DUMP_SAMPLE + 5, generator=g, dtype=torch.float64)
+    small = torch.randn(4, 3, generator=g).to(torch.bfloat16)
+    nograd = torch.randn(6, generator=g)
+    big.grad = big * 2
+    small.grad = small + 1
+    loss, logits = torch.tensor(0.625), torch.randn(5, 13, generator=g)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, torch.tensor(1.5), logits,
+                           [big, small, nograd])
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["grad_norm", "grads_sample", "logits", "loss", "params_sample"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    for k, v in got.items():   # the same positions on every call
+        assert np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy")))
+    assert got["loss"].tolist() == [0.625] and got["grad_norm"].tolist() == [1.5]
+    assert np.array_equal(got["logits"], logits.numpy())
+    n = bench.DUMP_SAMPLE
+    ps, gs = got["params_sample"], got["grads_sample"]
+    assert ps.shape == gs.shape == (n + 12 + 6,)
+    # the sampled positions are elements of the tensor, and the gradient is taken at the same ones
+    assert np.isin(ps[:n], big.float().numpy()).all() and len(np.unique(ps[:n])) > n // 2
+    assert np.array_equal(gs[:n], (ps[:n].astype(np.float64) * 2).astype(np.float32))
+    assert np.array_equal(ps[n:n + 12], small.float().reshape(-1).numpy())
+    assert np.array_equal(gs[n:n + 12], small.grad.float().reshape(-1).numpy())
+    assert np.array_equal(ps[n + 12:], nograd.numpy()) and not gs[n + 12:].any()

@@ -27,10 +27,10 @@ if has abtest; then
       --timeout ${TT:-120} --timeout-method thread
   done
 fi
-has bench && step bench 600 python bench.py --steps "$steps" --warmup 5 ${BA:-}
-has c5 && step c5 600 python bench.py --config c5 --steps "$steps" --warmup 5 --no-cpu-baseline
-has c2 && step c2 600 python bench.py --config c2 --steps "$steps" --warmup 5 --no-cpu-baseline
-has c3 && step c3 600 python bench.py --config c3 --steps "$steps" --warmup 5 --no-cpu-baseline
+has bench && step bench 600 python bench.py --full --steps "$steps" --warmup 5 ${BA:-}
+has c5 && step c5 600 python bench.py --full --config c5 --steps "$steps" --warmup 5 --no-cpu-baseline
+has c2 && step c2 600 python bench.py --full --config c2 --steps "$steps" --warmup 5 --no-cpu-baseline
+has c3 && step c3 600 python bench.py --full --config c3 --steps "$steps" --warmup 5 --no-cpu-baseline
 has host && step host 300 python tools/host_profile.py --config ${HC:-c4} --steps 5
 # the one-rank RCCL rehearsal of the data-parallel step, once per arm of AB_VAR
 if has rehab; then
