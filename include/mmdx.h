@@ -257,6 +257,31 @@ int mmdx_bn_bwd_masked_dy(int dtype, int train, const void* x, const void* dy,
                           const float* bn_beta, const float* save_mean,
                           const float* save_rstd, void* dx, float* dgamma, float* dbeta,
                           float beta_acc, void* workspace, size_t ws_bytes, void* stream);
+/* The two BatchNorm backwards at the end of a block with a downsample branch
+ * (torchvision Bottleneck / BasicBlock: out = relu(bn3(conv3) + downsample(x)), TP:279-289) in
+ * one reduce, one finalize and one apply pass.  Both read the same upstream gradient
+ * g = dy with the block's 1-bit ReLU mask applied: side a (the residual unit's BN) as
+ * mmdx_bn_bwd_ex(relu = 1, relu_mask = dy_mask, d_residual = NULL) does, side b (the
+ * downsample BN) as mmdx_bn_bwd_masked_dy does.  dy and the mask are streamed twice instead of
+ * four times; every output is bit-identical to the two separate calls.  Both sides are
+ * [rows][C].  workspace: mmdx_bn_pair_workspace_size(rows, C) bytes. */
+typedef struct {
+  const void* x;           /* the BN's input (its conv's raw output) */
+  const float* gamma;
+  const float* bn_beta;
+  const float* save_mean;
+  const float* save_rstd;
+  void* dx;
+  float* dgamma;
+  float* dbeta;
+} mmdx_bn_side;
+size_t mmdx_bn_pair_workspace_size(long rows, int C);
+int mmdx_bn_bwd_pair(int dtype, int train, const void* dy, const uint8_t* dy_mask, long rows,
+                     int C, const mmdx_bn_side* a, const mmdx_bn_side* b, float beta_acc,
+                     void* workspace, size_t ws_bytes, void* stream);
+/* MMDX_BN_BWD_PAIR (default 1): whether the ResNet trunk's backward plan issues
+ * mmdx_bn_bwd_pair for its downsample blocks (0: the two separate calls, for A/B runs). */
+int mmdx_bn_bwd_pair_enabled(void);
 /* stat_part (optional, [C][stat_blocks] pairs (sum g, sum g*xhat)): the reduction already
  * made by mmdx_conv_dgrad_bnstat in the epilogue that produced dy — the BN backward then
  * skips its own pass over (dy, x).  ReLU units only (with y = the unit's output for a
@@ -307,7 +332,11 @@ enum {
   MMDX_OP_LN_BWD_DROP, MMDX_OP_GEMM_BIAS_GRAD,
   /* (42: the retired conv + fused BN finalize op, tools/lab/RETIRED.md) and the BN apply pass
    * (i: C, relu; l: rows; p: x, residual, scale, shift, y, relu_mask) */
-  MMDX_OP_RETIRED_42, MMDX_OP_BN_APPLY
+  MMDX_OP_RETIRED_42, MMDX_OP_BN_APPLY,
+  /* mmdx_bn_bwd_pair (i: train, C; l: rows, ws_bytes; f: beta_acc; p: dy, dy_mask, x_a, dx_a,
+   * dgamma_a, dbeta_a, x_b, dx_b, dgamma_b, dbeta_b, ws, and a host table of 8 const float*:
+   * gamma, bn_beta, save_mean, save_rstd of side a, then of side b) */
+  MMDX_OP_BN_BWD_PAIR
 };
 typedef struct {
   int op, dtype, stream;

@@ -42,6 +42,12 @@ class PackItem(C.Structure):
                 ("c_master", C.c_int), ("RS", C.c_int), ("first_block", C.c_long)]
 
 
+class BnSide(C.Structure):
+    """mmdx_bn_side (include/mmdx.h): one of the two BatchNorms of mmdx_bn_bwd_pair."""
+    _fields_ = [("x", vp), ("gamma", vp), ("bn_beta", vp), ("save_mean", vp),
+                ("save_rstd", vp), ("dx", vp), ("dgamma", vp), ("dbeta", vp)]
+
+
 class PlanOp(C.Structure):
     """mmdx_plan_op (include/mmdx.h): one recorded operation of a launch plan."""
     _fields_ = [("op", C.c_int), ("dtype", C.c_int), ("stream", C.c_int), ("i", C.c_int * 8),
@@ -57,7 +63,8 @@ class PlanOp(C.Structure):
  OP_MAXPOOL_BN_FWD, OP_BN_BWD_POOL, OP_CONV_DGRAD_ACCMASK, OP_BN_BWD_MASKED_DY,
  OP_GEMM, OP_ATTN_FWD, OP_ATTN_BWD, OP_LN_FWD, OP_LN_BWD, OP_GELU_BWD, OP_BIAS_GRAD, OP_ADD,
  OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_AXPBY, OP_ATTN_FWD_LSE, OP_ATTN_BWD_LSE, OP_LN_FWD_DROP,
- OP_LN_BWD_DROP, OP_GEMM_BIAS_GRAD, OP_RETIRED_42, OP_BN_APPLY) = range(1, 44)
+ OP_LN_BWD_DROP, OP_GEMM_BIAS_GRAD, OP_RETIRED_42, OP_BN_APPLY,
+ OP_BN_BWD_PAIR) = range(1, 45)
 
 # name -> (restype, argtypes).  Kept in header order; tests check this table against
 # include/mmdx.h so the binding cannot drift from the ABI.
@@ -103,6 +110,10 @@ SIGNATURES = {
                                     f32, vp, sz, vp]),
     "mmdx_bn_bwd_ex": (i32, [i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, i32, vp,
                              vp, vp, vp, f32, vp, vp, sz, vp]),
+    "mmdx_bn_pair_workspace_size": (sz, [i64, i32]),
+    "mmdx_bn_bwd_pair": (i32, [i32, i32, vp, vp, i64, i32, C.POINTER(BnSide), C.POINTER(BnSide),
+                               f32, vp, sz, vp]),
+    "mmdx_bn_bwd_pair_enabled": (i32, []),
     "mmdx_bn_bwd_pool": (i32, [i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
                                i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, sz, vp]),
     "mmdx_img_desc_size": (sz, []),

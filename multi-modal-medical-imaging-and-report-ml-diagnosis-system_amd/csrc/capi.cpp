@@ -51,6 +51,7 @@ static Knobs read_knobs() {
   k.attn_fwd_nw = (int)env_long("MMDX_ATTN_FWD_NW", 0);
   k.attn_bwd_nw = (int)env_long("MMDX_ATTN_BWD_NW", 0);
   k.lstm_bwd_probe = env_long("MMDX_LSTM_BWD_PROBE", 0) != 0;
+  k.bn_bwd_pair = env_long("MMDX_BN_BWD_PAIR", 1) != 0;
   return k;
 }
 
@@ -69,6 +70,8 @@ extern "C" int mmdx_reload_config(void) {
   mmdx::g_knobs = mmdx::read_knobs();
   return 0;
 }
+
+extern "C" int mmdx_bn_bwd_pair_enabled(void) { return mmdx::knobs().bn_bwd_pair ? 1 : 0; }
 
 // A HIP stream restricted to `cus` of the device's compute units (0 or >= the device's
 // count: all of them), spread evenly over the mask so every XCD keeps its share; priority as

@@ -45,6 +45,7 @@ struct Knobs {
   int attn_fwd_nw;        // MMDX_ATTN_FWD_NW: raw value (0 = unset)
   int attn_bwd_nw;        // MMDX_ATTN_BWD_NW: raw value (0 = unset)
   bool lstm_bwd_probe;    // MMDX_LSTM_BWD_PROBE: lab phase stamps (tools/lab/lstm_probe.py)
+  bool bn_bwd_pair;       // MMDX_BN_BWD_PAIR (default on): mmdx_bn_bwd_pair_enabled()
 };
 const Knobs& knobs();
 

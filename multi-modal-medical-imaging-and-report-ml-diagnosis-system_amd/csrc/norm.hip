@@ -681,6 +681,162 @@ static int bn_bwd_t(int train, const void* x, const void* y, const G& dy, long r
   return 0;
 }
 
+// ---- the two BN backwards of a downsample block (bn3 of the residual unit, side a; the
+// downsample BN, side b) over ONE pass over their shared upstream gradient.  Both see
+// g = mask ? dy : 0 (side a as MODE 1 of the kernels above, side b as MaskedGrad with MODE 0).
+// Grid, per-thread row order, LDS merge order and the arithmetic are bn_bwd_reduce_kernel's /
+// bn_bwd_apply_body's, so each side's slabs, coefficients and dx are bit-identical to the
+// separate launches.
+//
+// Reduce: a 512-thread block; threads [0, 256) are bn_bwd_reduce_kernel's block for side a,
+// threads [256, 512) the same block for side b.  The two halves load the same dy vectors and
+// mask bytes at the same time from the same CU, so HBM serves them once, and each thread
+// keeps one side's accumulators only: 8 accumulator sets in one thread (sum g, sum g*xhat_a,
+// sum g*xhat_b plus both sides' mean / rstd) cost 110 VGPRs = 4 waves per SIMD, and spilled
+// under a 6-wave target.
+template <typename T>
+__global__ __launch_bounds__(2 * BN_NT) void bn_bwd_pair_reduce_kernel(
+    const T* __restrict__ xa, const T* __restrict__ xb, const T* __restrict__ dy,
+    const uint8_t* __restrict__ mask, long rows, int C, int ct, long rpb,
+    const float* __restrict__ mean_a, const float* __restrict__ rstd_a,
+    const float* __restrict__ mean_b, const float* __restrict__ rstd_b,
+    float2* __restrict__ part_a, float2* __restrict__ part_b) {
+  typedef typename Vec16<T>::type V;
+  constexpr int VEC = Vec16<T>::N;
+  __shared__ float s_a[2][BN_NT * VEC], s_b[2][BN_NT * VEC];
+  const int side = threadIdx.x / BN_NT, t = threadIdx.x % BN_NT;  // (wave-uniform)
+  const T* __restrict__ x = side ? xb : xa;
+  const float* __restrict__ mean = side ? mean_b : mean_a;
+  const float* __restrict__ rstd = side ? rstd_b : rstd_a;
+  float2* __restrict__ part = side ? part_b : part_a;
+  const int tx = t % ct, ty = t / ct, rt = BN_NT / ct;
+  const int c0 = (blockIdx.y * ct + tx) * VEC;
+  const long r0 = blockIdx.x * rpb, r1 = min(rows, r0 + rpb);
+  float sg[VEC], sgx[VEC], mu[VEC], rs[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) sg[j] = sgx[j] = mu[j] = rs[j] = 0.f;
+  if (c0 < C) {
+    load_coef<VEC>(mean + c0, mu);
+    load_coef<VEC>(rstd + c0, rs);
+    for (long r = r0 + ty; r < r1; r += rt) {
+      // plain loads: the other half of the block and the apply pass read them again
+      const V vx = *(const V*)(x + r * C + c0);
+      const V vd = *(const V*)(dy + r * C + c0);
+      const unsigned mb = mask[r * (C / VEC) + c0 / VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float g = to_f(vd[j]);
+        if (!((mb >> j) & 1u)) g = 0.f;
+        sg[j] += g;
+        sgx[j] += g * (to_f(vx[j]) - mu[j]) * rs[j];
+      }
+    }
+  }
+  const int me = ty * ct + tx;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    s_a[side][me * VEC + j] = sg[j];
+    s_b[side][me * VEC + j] = sgx[j];
+  }
+  __syncthreads();
+  if (ty == 0 && c0 < C) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      float a = 0.f, b = 0.f;
+      for (int yy = 0; yy < rt; ++yy) {
+        a += s_a[side][(yy * ct + tx) * VEC + j];
+        b += s_b[side][(yy * ct + tx) * VEC + j];
+      }
+      part[(long)(c0 + j) * gridDim.x + blockIdx.x] = make_float2(a, b);
+    }
+  }
+}
+
+// one finalize launch for both sides: blockIdx.y picks the side
+template <int TPC>
+__global__ __launch_bounds__(256) void bn_bwd_finalize_pair_kernel(BnBwdFinArgs a,
+                                                                   BnBwdFinArgs b) {
+  __shared__ float red[4];
+  bn_bwd_finalize_body<TPC>(blockIdx.y == 0 ? a : b, blockIdx.x, red);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void
+bn_bwd_pair_apply_kernel(
+    const T* __restrict__ xa, const T* __restrict__ xb, const T* __restrict__ dy,
+    const uint8_t* __restrict__ mask, long rows, int C, const float* __restrict__ coef_a,
+    const float* __restrict__ coef_b, T* __restrict__ dxa, T* __restrict__ dxb) {
+  typedef typename Vec16<T>::type V;
+  constexpr int VEC = Vec16<T>::N;
+  const RowTile rt = row_tile(C, VEC);
+  const int j0 = threadIdx.x % rt.tpr, ro = threadIdx.x / rt.tpr;
+  for (int j = j0; j < rt.cv; j += rt.tpr) {
+    float aa[VEC], ab[VEC], ak[VEC], ba[VEC], bb[VEC], bk[VEC];
+    load_coef<VEC>(coef_a + j * VEC, aa);
+    load_coef<VEC>(coef_a + C + j * VEC, ab);
+    load_coef<VEC>(coef_a + 2 * C + j * VEC, ak);
+    load_coef<VEC>(coef_b + j * VEC, ba);
+    load_coef<VEC>(coef_b + C + j * VEC, bb);
+    load_coef<VEC>(coef_b + 2 * C + j * VEC, bk);
+    for (long r = (long)blockIdx.x * rt.rpi + ro; r < rows; r += (long)gridDim.x * rt.rpi) {
+      const long i = r * rt.cv + j;
+      // every operand's last read of the step (the block's conv1 dgrad accumulates onto its
+      // own output, not onto dy): nontemporal, as in bn_bwd_load
+      const V va = __builtin_nontemporal_load((const V*)xa + i);
+      const V vb = __builtin_nontemporal_load((const V*)xb + i);
+      const V vd = __builtin_nontemporal_load((const V*)dy + i);
+      const unsigned mb = mask[i];
+      V oa, ob;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float g = to_f(vd[e]);
+        if (!((mb >> e) & 1u)) g = 0.f;
+        oa[e] = from_f<T>(fmaf(ak[e], to_f(va[e]), fmaf(aa[e], g, ab[e])));
+        ob[e] = from_f<T>(fmaf(bk[e], to_f(vb[e]), fmaf(ba[e], g, bb[e])));
+      }
+      ((V*)dxa)[i] = oa;
+      ((V*)dxb)[i] = ob;
+    }
+  }
+}
+
+template <typename T>
+static int bn_bwd_pair_t(int train, const void* dy, const uint8_t* mask, long rows, int C,
+                         const mmdx_bn_side& a, const mmdx_bn_side& b, float beta_acc, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+  constexpr int VEC = Vec16<T>::N;
+  MMDX_CHECK_ARG(C % VEC == 0, "bn bwd pair: C=%d must be a multiple of %d", C, VEC);
+  const BnLayout L = bn_layout(rows, C, VEC);
+  const size_t part_bytes = (size_t)L.rblocks * C * sizeof(float2);
+  const size_t side = part_bytes + 5 * (size_t)C * sizeof(float);  // a multiple of 16 B
+  MMDX_CHECK_ARG(ws && ws_bytes >= 2 * side, "bn bwd pair: workspace %zu < %zu", ws_bytes,
+                 2 * side);
+  float2* part_a = (float2*)ws;
+  float* coef_a = (float*)((char*)ws + part_bytes);
+  float2* part_b = (float2*)((char*)ws + side);
+  float* coef_b = (float*)((char*)ws + side + part_bytes);
+  const int nblk = L.rblocks;
+  hipLaunchKernelGGL(bn_bwd_pair_reduce_kernel<T>, dim3(L.rblocks, L.cgroups), dim3(2 * BN_NT), 0,
+                     st, (const T*)a.x, (const T*)b.x, (const T*)dy, mask, rows, C, L.ct,
+                     L.rows_per_block, a.save_mean, a.save_rstd, b.save_mean, b.save_rstd, part_a,
+                     part_b);
+  const BnBwdFinArgs fa{(const float2*)part_a, nblk, rows, C, train, a.gamma, a.bn_beta,
+                        a.save_mean, a.save_rstd, a.dgamma, a.dbeta, beta_acc, coef_a};
+  const BnBwdFinArgs fb{(const float2*)part_b, nblk, rows, C, train, b.gamma, b.bn_beta,
+                        b.save_mean, b.save_rstd, b.dgamma, b.dbeta, beta_acc, coef_b};
+  const bool wide = nblk > fin_wide();
+  const int nfin = wide ? C : (C + FIN_W - 1) / FIN_W;
+  if (wide)
+    hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel<256>, dim3(nfin, 2), dim3(256), 0, st, fa, fb);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel<64>, dim3(nfin, 2), dim3(256), 0, st, fa, fb);
+  hipLaunchKernelGGL(bn_bwd_pair_apply_kernel<T>, dim3(grid_rows(rows, C, VEC)), dim3(256), 0, st,
+                     (const T*)a.x, (const T*)b.x, (const T*)dy, mask, rows, C,
+                     (const float*)coef_a, (const float*)coef_b, (T*)a.dx, (T*)b.dx);
+  MMDX_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------------ LayerNorm
 // One wave per row; D <= 64 * LN_MAXV * VEC handled from registers (two-pass stats).
 constexpr int LN_MAXV = 4;
@@ -1077,6 +1233,24 @@ extern "C" int mmdx_bn_bwd_masked_dy(int dtype, int train, const void* x, const 
   return bn_bwd_t<float>(train, x, nullptr, MaskedGrad<float>{(const float*)dy, dy_mask, C},
                          rows, C, gamma, bn_beta, save_mean, save_rstd, 0, nullptr, 0, dx,
                          nullptr, dgamma, dbeta, beta_acc, ws, ws_bytes, st);
+}
+
+extern "C" size_t mmdx_bn_pair_workspace_size(long rows, int C) {
+  return 2 * mmdx_bn_workspace_size(rows, C);  // per side: its slabs and its coefficients
+}
+
+extern "C" int mmdx_bn_bwd_pair(int dtype, int train, const void* dy, const uint8_t* dy_mask,
+                                long rows, int C, const mmdx_bn_side* a, const mmdx_bn_side* b,
+                                float beta_acc, void* ws, size_t ws_bytes, void* stream) {
+  MMDX_CHECK_ARG(dtype != F16, "mmdx_bn_bwd_pair: fp16 is the C5 path only");
+  MMDX_CHECK_ARG(rows > 0 && C > 0 && dy && dy_mask && a && b, "bn bwd pair: bad args");
+  MMDX_CHECK_ARG(a->x && a->dx && a->save_mean && a->save_rstd && b->x && b->dx &&
+                     b->save_mean && b->save_rstd && a->dx != b->dx,
+                 "bn bwd pair: each side needs x, dx, save_mean and save_rstd");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == BF16)
+    return bn_bwd_pair_t<bf16>(train, dy, dy_mask, rows, C, *a, *b, beta_acc, ws, ws_bytes, st);
+  return bn_bwd_pair_t<float>(train, dy, dy_mask, rows, C, *a, *b, beta_acc, ws, ws_bytes, st);
 }
 
 extern "C" int mmdx_bn_bwd(int dtype, int train, const void* x, const void* y, const void* dy,

@@ -114,6 +114,22 @@ int run_one(const mmdx_plan_op& o, void* const* ext, void* const* events, void* 
                                    (const float*)P(o, 5, ext), (const float*)P(o, 6, ext),
                                    P(o, 7, ext), (float*)P(o, 8, ext), (float*)P(o, 9, ext),
                                    o.f[0], P(o, 10, ext), (size_t)o.l[1], s);
+    case MMDX_OP_BN_BWD_PAIR: {
+      // i: train, C; l: rows, ws_bytes; f: beta_acc
+      // p: dy, dy_mask, x_a, dx_a, dgamma_a, dbeta_a, x_b, dx_b, dgamma_b, dbeta_b, ws,
+      //    host table {gamma, beta, mean, rstd} of side a, then of side b
+      const float* const* t = (const float* const*)P(o, 11, ext);
+      if (!t) {
+        mmdx_set_error("plan: bn bwd pair without its parameter table");
+        return -22;
+      }
+      const mmdx_bn_side a{P(o, 2, ext), t[0], t[1], t[2], t[3], P(o, 3, ext),
+                           (float*)P(o, 4, ext), (float*)P(o, 5, ext)};
+      const mmdx_bn_side b{P(o, 6, ext), t[4], t[5], t[6], t[7], P(o, 7, ext),
+                           (float*)P(o, 8, ext), (float*)P(o, 9, ext)};
+      return mmdx_bn_bwd_pair(o.dtype, o.i[0], P(o, 0, ext), (const uint8_t*)P(o, 1, ext),
+                              o.l[0], o.i[1], &a, &b, o.f[0], P(o, 10, ext), (size_t)o.l[1], s);
+    }
     case MMDX_OP_CONV_DGRAD_ACCMASK:
       // p: dy, w_crsk, dx, acc_src, acc_mask
       return mmdx_conv_dgrad_accmask(o.dtype, &o.d, P(o, 0, ext), P(o, 1, ext), P(o, 2, ext),

@@ -558,27 +558,56 @@ class _Plan:
             def xref(x):
                 return _Ext(2) if isinstance(x, _Ext) else x
 
+            def bwd_fields(u, dout, dout_mask, kind):
+                # kept for the per-launch parity test (tests/test_trunk_launches_gpu.py):
+                # the BN backward's upstream gradient and where its ReLU mask comes from
+                u["dconv"] = A.new(tuple(u["y"].shape), T, dev)
+                u["dout"], u["dout_mask"], u["bwd_kind"] = dout, dout_mask, kind
+                return u["dconv"]
+
+            def wgrad(u):
+                """u's weight gradient on the side stream (which already waits for u's dconv)."""
+                d, cv, dconv = u["d"], u["conv"], u["dconv"]
+                wsn = L.lib().mmdx_conv_wgrad_workspace_size(dt, d)
+                ws_for(wsn, 1)
+                if u["pair"]:  # pair-conv gradient [K][8][R][S2], mapped to the master layout
+                    dwp = A.new((d.K, d.C, d.R, d.S), torch.float32, dev)
+                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt, i=(d.C,),
+                             l=(wsn,),
+                             f=(0.0,), p=(xref(u["x"]), dconv, dwp, _WS2), d=d)
+                    bw.add(L.OP_STEM_PAIR_GRAD, stream=1,
+                           i=(d.K, cv.in_channels, cv.kernel_size, cv.kernel_size), f=(0.0,),
+                           p=(dwp, g(cv.weight)))
+                else:
+                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt,
+                             i=(u["cm"],),
+                             l=(wsn,), f=(0.0,), p=(xref(u["x"]), dconv, g(cv.weight), _WS2),
+                             d=d)
+
             def unit_bwd(u, dout, want_dx, dx_acc=None, want_res=False, stats=None,
-                         feed=None, pool=None, no_dres=False, acc=None, dout_mask=None):
+                         feed=None, pool=None, no_dres=False, acc=None, dout_mask=None,
+                         pair_ds=None, bn_done=False):
                 """BN(+res)(+ReLU) backward, wgrad (side stream), dgrad.  `stats`: this
                 unit's BN-backward partials, already made by the dgrad that produced `dout`;
                 `feed`: the unit whose dout this unit's dgrad produces (no residual) — its
-                partials are then made in the dgrad epilogue and returned."""
+                partials are then made in the dgrad epilogue and returned.  `pair_ds`: the
+                block's downsample unit, whose BN backward (upstream gradient: `dout` under
+                this unit's ReLU bit mask) and wgrad are issued here with this unit's
+                (mmdx_bn_bwd_pair); its later call passes `bn_done` and adds the dgrad only."""
                 d = u["d"]
                 K = d.K
                 rows = d.N * d.P * d.Q
-                dconv = A.new(tuple(u["y"].shape), T, dev)
-                u["dconv"] = dconv
-                # kept for the per-launch parity test (tests/test_trunk_launches_gpu.py):
-                # the BN backward's upstream gradient and where its ReLU mask comes from
-                u["dout"], u["dout_mask"] = dout, dout_mask
-                u["bwd_kind"] = ("masked" if dout_mask is not None else
-                                 "pool" if pool is not None else
-                                 "res" if want_res else "relu" if u["relu"] else "plain")
+                if bn_done:
+                    dconv = u["dconv"]
+                else:
+                    dconv = bwd_fields(u, dout, dout_mask,
+                                       "masked" if dout_mask is not None else
+                                       "pool" if pool is not None else
+                                       "res" if want_res else "relu" if u["relu"] else "plain")
                 # no_dres: the identity path's gradient is added by conv1's dgrad epilogue
                 # from (dout, ReLU bit mask) instead (mmdx_conv_dgrad_accmask)
-                dres = (A.new(tuple(u["y"].shape), T, dev) if want_res and not no_dres
-                        else None)
+                dres = (A.new(tuple(u["y"].shape), T, dev)
+                        if want_res and not no_dres and not bn_done else None)
                 wsn = L.lib().mmdx_bn_workspace_size(rows, K)
                 ws_for(wsn)
                 # ReLU mask: a residual unit's bit mask from the forward (else its output);
@@ -586,7 +615,26 @@ class _Plan:
                 rmask = u.get("rmask") if want_res else None
                 out = u["out"] if want_res and rmask is None else None
                 sp, sb = stats if stats is not None else (None, 0)
-                if dout_mask is not None:
+                if bn_done:
+                    pass
+                elif pair_ds is not None:
+                    # bn3 and the downsample BN read the same masked gradient: one reduce, one
+                    # finalize and one apply for both (mmdx_bn_bwd_pair)
+                    v = pair_ds
+                    assert rmask is not None and dres is None and sp is None
+                    assert tuple(v["y"].shape) == tuple(u["y"].shape)
+                    dconv_b = bwd_fields(v, dout, rmask, "masked")
+                    wsn = L.lib().mmdx_bn_pair_workspace_size(rows, K)
+                    ws_for(wsn)
+                    tab = (ctypes.c_void_p * 8)(*[t.data_ptr() for w in (u, v) for t in
+                                                  (w["bn"].weight, w["bn"].bias, w["mean"],
+                                                   w["rstd"])])
+                    A.bufs.append(tab)  # host table the op points at: lives with the plan
+                    bw.add(L.OP_BN_BWD_PAIR, dt, i=(int(train), K), l=(rows, wsn), f=(0.0,),
+                           p=(dout, rmask, u["y"], dconv, g(u["bn"].weight), g(u["bn"].bias),
+                              v["y"], dconv_b, g(v["bn"].weight), g(v["bn"].bias), _WS,
+                              ctypes.addressof(tab)))
+                elif dout_mask is not None:
                     # a downsample BN: its upstream gradient is the residual unit's dout with
                     # that unit's ReLU bit mask applied on the fly (mmdx_bn_bwd_masked_dy)
                     bw.add(L.OP_BN_BWD_MASKED_DY, dt, i=(int(train), K), l=(rows, wsn),
@@ -609,25 +657,14 @@ class _Plan:
                            p=(u["y"], out, dout, u["bn"].weight, u["bn"].bias, u["mean"],
                               u["rstd"], dconv, dres, g(u["bn"].weight), g(u["bn"].bias),
                               _WS))
-                wsn = L.lib().mmdx_conv_wgrad_workspace_size(dt, d)
-                ws_for(wsn, 1)
-                ev = A.event()
-                bw.add(L.OP_SIGNAL, p=(ev,), stream=0)
-                bw.add(L.OP_WAIT, p=(ev,), stream=1)
-                cv = u["conv"]
-                if u["pair"]:  # pair-conv gradient [K][8][R][S2], mapped to the master layout
-                    dwp = A.new((d.K, d.C, d.R, d.S), torch.float32, dev)
-                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt, i=(d.C,),
-                             l=(wsn,),
-                             f=(0.0,), p=(xref(u["x"]), dconv, dwp, _WS2), d=d)
-                    bw.add(L.OP_STEM_PAIR_GRAD, stream=1,
-                           i=(d.K, cv.in_channels, cv.kernel_size, cv.kernel_size), f=(0.0,),
-                           p=(dwp, g(cv.weight)))
-                else:
-                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt,
-                             i=(u["cm"],),
-                             l=(wsn,), f=(0.0,), p=(xref(u["x"]), dconv, g(cv.weight), _WS2),
-                             d=d)
+                if not bn_done:
+                    # one event after the BN backward(s): the side stream's wgrads wait on it
+                    ev = A.event()
+                    bw.add(L.OP_SIGNAL, p=(ev,), stream=0)
+                    bw.add(L.OP_WAIT, p=(ev,), stream=1)
+                    wgrad(u)
+                    if pair_ds is not None:
+                        wgrad(pair_ds)
                 dx, fed = None, None
                 if want_dx:
                     if dx_acc is not None:
@@ -659,6 +696,8 @@ class _Plan:
                 u["dx"] = dx
                 return dx, dres, fed
 
+            # MMDX_BN_BWD_PAIR=0: the two separate BN backwards (A/B runs)
+            pair_on = bool(L.lib().mmdx_bn_bwd_pair_enabled())
             N_, H_, W_, C_ = self.out_geom
             dx = A.new((N_, H_, W_, C_), T, dev)
             self.dtop = dx
@@ -703,11 +742,15 @@ class _Plan:
                 mask_id = (T == torch.bfloat16 and len(bu) > 1
                            and bu[-1].get("rmask") is not None)
                 acc_id = mask_id and ds_u is None
+                # downsample block: its two BN backwards run as one paired op, issued where
+                # bn3's is, and the downsample wgrad follows conv3's on the side stream
+                paired = mask_id and ds_u is not None and pair_on
                 dh, dres, fed = unit_bwd(bu[-1], dx, True, want_res=True,
                                          feed=bu[-2] if len(bu) > 1 else None,
-                                         no_dres=mask_id)
+                                         no_dres=mask_id, pair_ds=ds_u if paired else None)
                 blk_dout = dx
-                ds_in = dict(dout_mask=bu[-1]["rmask"]) if mask_id else {}
+                ds_in = (dict(bn_done=True) if paired else
+                         dict(dout_mask=bu[-1]["rmask"]) if mask_id else {})
                 ds_dout = blk_dout if mask_id else dres
                 for k in range(len(bu) - 2, -1, -1):
                     uu = bu[k]
@@ -878,7 +921,7 @@ class _TrunkFn(torch.autograd.Function):
             if x.dtype != T:
                 raise TypeError("NHWC trunk input must already be in the compute dtype")
         key = (N, H, W, cin, in_nchw, T, train, keep, dev.index,
-               tuple(p.data_ptr() for p in params))
+               tuple(p.data_ptr() for p in params), L.lib().mmdx_bn_bwd_pair_enabled())
         plan = _plans_for(trunk, key,
                           lambda: _Plan(trunk, N, H, W, in_nchw, cin, T, train, keep, dev))
         # the downsample branches run on the side stream (joined inside the plan)
