@@ -200,9 +200,13 @@ int mmdx_stem_pair_grad(const float* dw_pair, int K, int C, int R, int S, float*
  * save_mean/save_rstd: [C] fp32, consumed by the backward.
  * Replaces: BatchNorm2d + ReLU (+ Bottleneck residual add) inside the resnet trunk
  * (train mode: unfreeze_backbone TP:223; eval: freeze_backbone TP:206, IP:170). */
+/* Enough for either dtype (fp32 needs C % 4 == 0, bf16 C % 8 == 0; sized for the widths C is
+ * a multiple of); 0 when C fits neither, which no entry point accepts as a workspace. */
 size_t mmdx_bn_workspace_size(long rows, int C);
 /* stat_part: optional precomputed per-block (mean, M2) pairs [C][stat_blocks] over
- * consecutive stat_rows-row blocks (e.g. from mmdx_conv_fwd's epilogue); NULL = reduce x. */
+ * consecutive stat_rows-row blocks (e.g. from mmdx_conv_fwd's epilogue); NULL = reduce x.
+ * The blocks must cover the rows exactly, the last one holding 1..stat_rows of them:
+ * (stat_blocks - 1) * stat_rows < rows <= stat_blocks * stat_rows, else an error. */
 int mmdx_bn_fwd(int dtype, int train, const void* x, long rows, int C,
                 const float* stat_part, int stat_blocks, long stat_rows,
                 const float* gamma, const float* beta, float* running_mean,

@@ -3,7 +3,12 @@
 // BN statistics are reduced deterministically: every block writes a per-channel
 // (mean, M2) partial over its row slab, and a finalize kernel merges the slabs in a
 // fixed order with Chan's parallel-variance update (no float atomics, bitwise
-// reproducible, no E[x^2]-E[x]^2 cancellation across the 10^5..10^6 rows of a layer).
+// reproducible, no E[x^2]-E[x]^2 cancellation BETWEEN slabs or between the threads of a
+// block: those merges work on (mean, M2) pairs).  Inside one thread bn_stats_kernel does form
+// sum d^2 - (sum d)^2 / n in fp32 over its own rows_per_block / rt rows, with d = x minus the
+// thread's first row, so what cancels there is the spread of those rows around that row, not
+// the channel's mean (measured at 1 and at 4 rows per thread with |mean| up to 64 standard
+// deviations: DESIGN §9).
 // All elementwise passes move 16 B per lane (8 bf16 / 4 fp32).
 #include <algorithm>
 #include <type_traits>
@@ -63,18 +68,30 @@ __global__ __launch_bounds__(BN_NT) void bn_stats_kernel(const T* __restrict__ x
   const int tx = threadIdx.x % ct, ty = threadIdx.x / ct, rt = BN_NT / ct;
   const int c0 = (blockIdx.y * ct + tx) * VEC;
   const long r0 = blockIdx.x * rpb, r1 = min(rows, r0 + rpb);
-  float sum[VEC], sq[VEC];
+  // Sums of d = x - pivot, the pivot being the thread's own first row: sum d^2 - (sum d)^2 / n
+  // then cancels against the spread of the thread's rows, not against the channel's mean
+  // (and a thread with one row has M2 = 0 exactly, which sum x^2 - x * x under fma
+  // contraction did not give).
+  float sum[VEC], sq[VEC], piv[VEC];
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) sum[j] = sq[j] = 0.f;
+  for (int j = 0; j < VEC; ++j) sum[j] = sq[j] = piv[j] = 0.f;
   int cnt = 0;
   if (c0 < C) {
-    for (long r = r0 + ty; r < r1; r += rt) {
+    long r = r0 + ty;
+    if (r < r1) {
+      const V v = *(const V*)(x + r * C + c0);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) piv[j] = to_f(v[j]);
+      cnt = 1;
+      r += rt;
+    }
+    for (; r < r1; r += rt) {
       const V v = *(const V*)(x + r * C + c0);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        const float f = to_f(v[j]);
-        sum[j] += f;
-        sq[j] += f * f;
+        const float d = to_f(v[j]) - piv[j];
+        sum[j] += d;
+        sq[j] += d * d;
       }
       ++cnt;
     }
@@ -83,8 +100,8 @@ __global__ __launch_bounds__(BN_NT) void bn_stats_kernel(const T* __restrict__ x
   s_n[me] = (float)cnt;
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    const float m = cnt ? sum[j] / cnt : 0.f;
-    s_mean[me * VEC + j] = m;
+    const float m = cnt ? sum[j] / cnt : 0.f;  // mean of d
+    s_mean[me * VEC + j] = piv[j] + m;
     s_m2[me * VEC + j] = cnt ? fmaxf(sq[j] - sum[j] * m, 0.f) : 0.f;
   }
   __syncthreads();
@@ -1108,10 +1125,21 @@ __global__ __launch_bounds__(1024) void ln_bwd_finalize_kernel(const float* __re
 
 using namespace mmdx;
 
+// stat_blocks consecutive stat_rows-row slabs cover `rows` exactly when the last one holds
+// between 1 and stat_rows rows: with fewer blocks rows are missing, with more the finalize's
+// weight of the last slab, rows - (stat_blocks - 1) * stat_rows, is zero or negative.
+static bool stat_slabs_cover(int stat_blocks, long stat_rows, long rows) {
+  return stat_blocks > 0 && stat_rows > 0 && (long)stat_blocks * stat_rows >= rows &&
+         (long)(stat_blocks - 1) * stat_rows < rows;
+}
+
+// Enough for either dtype's layout (fp32: 4 channels per vector, bf16: 8).  A width C is not a
+// multiple of is skipped (no kernel runs with it; C < 8 would give bn_layout zero channel
+// vectors); 0 when neither fits, which every caller's ws_bytes >= need check rejects.
 extern "C" size_t mmdx_bn_workspace_size(long rows, int C) {
-  const BnLayout L = bn_layout(rows, C, 4);  // fp32 layout has the most row blocks
-  const BnLayout L8 = bn_layout(rows, C, 8);
-  const int nb = std::max(L.rblocks, L8.rblocks);
+  if (C <= 0 || C % 4 != 0) return 0;
+  int nb = bn_layout(rows, C, 4).rblocks;
+  if (C % 8 == 0) nb = std::max(nb, bn_layout(rows, C, 8).rblocks);
   return (size_t)nb * C * sizeof(float2) + 5 * (size_t)C * sizeof(float);
 }
 
@@ -1123,8 +1151,7 @@ extern "C" int mmdx_bn_fwd_ex(int dtype, int train, const void* x, long rows, in
                               uint8_t* relu_mask, void* ws, size_t ws_bytes, void* stream) {
   MMDX_CHECK_ARG(dtype != F16, "mmdx_bn_fwd: fp16 is the C5 path only");
   MMDX_CHECK_ARG(rows > 0 && C > 0 && save_mean && save_rstd, "bn fwd: bad args");
-  MMDX_CHECK_ARG(!stat_part || (stat_blocks > 0 && stat_rows > 0 &&
-                                (long)stat_blocks * stat_rows >= rows),
+  MMDX_CHECK_ARG(!stat_part || stat_slabs_cover(stat_blocks, stat_rows, rows),
                  "bn fwd: bad precomputed statistics layout");
   MMDX_CHECK_ARG(!relu_mask || (relu && y), "bn fwd: a ReLU mask needs relu and y");
   hipStream_t st = (hipStream_t)stream;
@@ -1145,10 +1172,10 @@ extern "C" int mmdx_bn_finalize(const float* stat_part, int stat_blocks, long st
                                 float* running_mean, float* running_var, float momentum,
                                 float eps, float* save_mean, float* save_rstd, float* scale,
                                 float* shift, void* stream) {
-  MMDX_CHECK_ARG(stat_part && stat_blocks > 0 && stat_rows > 0 && rows > 0 && C > 0 &&
-                     (long)stat_blocks * stat_rows >= rows && save_mean && save_rstd && scale &&
-                     shift,
+  MMDX_CHECK_ARG(stat_part && rows > 0 && C > 0 && save_mean && save_rstd && scale && shift,
                  "bn finalize: bad args");
+  MMDX_CHECK_ARG(stat_slabs_cover(stat_blocks, stat_rows, rows),
+                 "bn finalize: bad precomputed statistics layout");
   hipStream_t st = (hipStream_t)stream;
   const BnFinArgs fa{(const float2*)stat_part, stat_blocks, rows, stat_rows, C, gamma, beta,
                      running_mean, running_var, momentum, eps, save_mean, save_rstd, scale,

@@ -50,6 +50,24 @@ def test_workspace_queries_are_host_only(lib):
     assert lib.mmdx_bn_workspace_size(128 * 56 * 56, 64) > 0
 
 
+def test_bn_workspace_size_skips_widths_c_is_no_multiple_of(lib):
+    """mmdx_bn_workspace_size sizes for the vector widths C is a multiple of (4 channels per
+    fp32 vector, 8 per bf16 one): C = 4 and C = 12 are legal fp32 BatchNorms without a bf16
+    layout (C = 4 used to divide by zero on the host), C = 8 has one bf16 vector, and a C no
+    kernel accepts gives 0, which every entry point's workspace check rejects."""
+    import bn_ref
+    assert lib.mmdx_bn_workspace_size(21, 4) == bn_ref.workspace_size(21, 4) == 4 * 8 + 5 * 4 * 4
+    for rows, C in [(21, 12), (1, 8), (37, 48), (5, 2304), (128 * 56 * 56, 64), (100000, 4)]:
+        want = bn_ref.workspace_size(rows, C)
+        nb = max(bn_ref._rblocks(rows, C, v) for v in (4, 8) if C % v == 0)
+        assert want == nb * C * 8 + 5 * C * 4 > 0
+        assert lib.mmdx_bn_workspace_size(rows, C) == want, (rows, C)
+        assert lib.mmdx_bn_pair_workspace_size(rows, C) == 2 * want, (rows, C)
+    for C in (0, 2, 6, -8):
+        assert lib.mmdx_bn_workspace_size(21, C) == 0
+        assert lib.mmdx_bn_pair_workspace_size(21, C) == 0
+
+
 def test_plan_op_layout_matches_c(lib):
     import ctypes
     import mmdx._lib as L

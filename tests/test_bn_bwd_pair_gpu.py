@@ -9,35 +9,9 @@ import pytest
 import torch
 
 import mmdx._lib as L
+from bn_ref import _wide_rows  # the mirror of csrc/norm.hip bn_layout lives in tests/bn_ref.py
 
 pytestmark = pytest.mark.gpu
-
-BN_NT = 256      # csrc/norm.hip: threads per reduce block
-FIN_WIDE = 512   # csrc/norm.hip fin_wide(): above this many slabs the wide finalize runs
-
-
-def _rblocks(rows, C, vec):
-    """Row slabs of csrc/norm.hip bn_layout(rows, C, vec)."""
-    cv = C // vec
-    ct = min(cv, 64)
-    rt = BN_NT // ct
-    cgroups = (cv + ct - 1) // ct
-    target = max(1, 2048 // cgroups)
-    rpb = max((rows + target - 1) // target, rt)
-    rpb = (rpb + rt - 1) // rt * rt
-    return (rows + rpb - 1) // rpb
-
-
-def _wide_rows(C):
-    """The fewest rows (plus a ragged tail) whose slab count exceeds fin_wide() in both the
-    bf16 and the fp32 layout."""
-    rt8 = BN_NT // min(C // 8, 64)
-    rows = (FIN_WIDE + 1) * rt8 + 5
-    assert _rblocks(rows, C, 8) > FIN_WIDE and _rblocks(rows, C, 4) > FIN_WIDE
-    # the mirror above against the library: its workspace holds max(slabs) * C pairs + 5 C
-    nb = max(_rblocks(rows, C, 4), _rblocks(rows, C, 8))
-    assert L.lib().mmdx_bn_workspace_size(rows, C) == nb * C * 8 + 5 * C * 4
-    return rows
 
 
 # (rows, C): < 256 channel vectors, several rows per block, ragged tail | 256 vectors (bf16) |
