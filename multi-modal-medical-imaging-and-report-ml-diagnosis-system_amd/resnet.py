@@ -12,6 +12,7 @@ with the residual-path gradient summed inside the dgrad epilogue (beta = 1).
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import math
 import weakref
@@ -21,6 +22,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import call, ptr, stream
+from .plan import (MAX_PLAN_KEYS, WS, WS2, _Arena, _Ext, _OpList, _Token,  # noqa: F401
+                   pack_multi_args, plan_cache_get)
 
 _VEC = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}
 
@@ -216,12 +219,12 @@ class ResNetTrunk(nn.Sequential):
 
 
 # ----------------------------------------------------------------------------- engine
-# The trunk is executed from launch plans (include/mmdx.h, csrc/plan.cpp): the forward and
-# the backward of one (batch shape, dtype, mode, parameter set) are recorded once as op
-# lists over a buffer arena, then every step replays each with ONE C call.  Per-call
-# buffers (the image batch, the upstream gradient, the gradient arena) enter as external
-# bases.  An arena holds one forward's saved activations until its backward has run, so a
-# second forward while a backward is pending records a second arena instead of clobbering.
+# The trunk is executed from launch plans (plan.py; include/mmdx.h, csrc/plan.cpp): the
+# forward and the backward of one (batch shape, dtype, mode, parameter set) are recorded once
+# as op lists over a buffer arena, then every step replays each with ONE C call.  _Rec
+# records one op per method; the _record_* / _block_* functions below sequence them and
+# _Plan.__init__ strings those together.  tools/plan_dump.py writes a recorded plan as
+# pointer-free text, to diff the planner of two revisions op for op (on the CPU).
 
 def _desc(N, H, W, C, conv):
     k, s, p = conv.kernel_size, conv.stride, conv.padding
@@ -230,583 +233,579 @@ def _desc(N, H, W, C, conv):
     return L.ConvDesc(N, H, W, C, conv.out_channels, k, k, s, s, p, p, P, Q)
 
 
-class _Ext:
-    """An operand taken from the per-call external base `k` (+ byte offset)."""
-    __slots__ = ("k", "off")
+@dataclasses.dataclass(eq=False)
+class _Unit:
+    """One conv + BN(+res)(+ReLU) of a recorded plan: what it is made of, then the arena
+    buffers its forward and its backward fill in (read by the per-launch parity test,
+    tests/test_trunk_launches_gpu.py).  A field that does not apply is None."""
+    conv: Conv2d
+    bn: BatchNorm2d
+    relu: bool
+    d: L.ConvDesc
+    in_hw: tuple          # true input H, W (the pair stem's d is over the pixel-pair image)
+    elt: int              # bytes per element of the compute dtype
+    x: object             # input: an arena buffer, or _Ext (the trunk input itself)
+    res: object = None    # residual added before the ReLU
+    pair: bool = False    # the stem as a conv over pixel pairs
+    # forward
+    y: object = None      # raw conv output (folded eval: never materialised)
+    out: object = None    # post-activation tensor (statistics-only BN: never written)
+    mean: object = None
+    rstd: object = None
+    wc: object = None     # CRSK weight copy the dgrad reads
+    rmask: object = None  # 1-bit ReLU mask of a residual unit
+    # backward
+    dconv: object = None      # the BN backward's output, read by wgrad and dgrad
+    dout: object = None       # the BN backward's upstream gradient ...
+    dout_mask: object = None  # ... and the ReLU bit mask applied to it on the fly
+    bwd_kind: str = None      # "plain" / "relu" / "res" / "masked" / "pool"
+    dx: object = None         # the tensor the dgrad wrote or accumulated onto
 
-    def __init__(self, k, off=0):
-        self.k, self.off = k, off
+    def cost(self, kind, extra=0):
+        d = self.d
+        return conv_cost(kind, self.conv, d.N, self.in_hw[0], self.in_hw[1], d.P, d.Q,
+                         self.elt, extra)
+
+    def in_bytes(self):
+        d = self.d
+        return d.N * d.H * d.W * d.C * self.elt
 
 
-class _OpList:
-    def __init__(self):
-        self.ops = []
-        self.conv_names = []   # per timed conv op, its tag (fwd / dgrad / wgrad)
+class _Rec:
+    """Records the trunk's C-ABI calls as plan ops, one method per op, and holds what a
+    recording shares: the arena, the two op lists, the dtype and mode, the workspace need per
+    stream, the weights awaiting the multi-tensor pack and the gradient layout."""
 
-    def add(self, code, dtype=0, i=(), l=(), f=(), p=(), d=None, stream=0):
-        o = L.PlanOp()
-        o.op, o.dtype, o.stream = code, dtype, stream
-        for j, v in enumerate(i):
-            o.i[j] = int(v)
-        for j, v in enumerate(l):
-            o.l[j] = int(v)
-        for j, v in enumerate(f):
-            o.f[j] = float(v)
-        for j in range(12):
-            o.ext[j] = -1
-        for j, v in enumerate(p):
-            if isinstance(v, _Ext):
-                o.ext[j] = v.k
-                o.p[j] = v.off
-            elif isinstance(v, torch.Tensor):
-                o.p[j] = v.data_ptr()
+    def __init__(self, trunk, N, T, train, keep, dev):
+        self.N, self.T, self.dt, self.vec = N, T, L.dtype_code(T), _VEC[T]
+        self.train, self.keep = train, keep
+        self.fold = not train and not keep   # eval-mode BN folded into the conv epilogue
+        self.arena = _Arena(dev)
+        self.fw = _OpList()
+        self.bw = _OpList() if keep else None
+        self.ws_need = [0, 0]  # per stream: 0 = main, 1 = weight-gradient side stream
+        self.packs = []
+        self.ev_pack = None
+        # the flat fp32 gradient arena, in engine_params order
+        self.grad_off = {}
+        off = 0
+        for prm in trunk.engine_params():
+            self.grad_off[id(prm)] = off
+            off += (prm.numel() * 4 + 15) // 16 * 16  # 16-B aligned, dense for ResNets
+        self.grad_bytes = off
+
+    def buf(self, shape, dtype=None):
+        return self.arena.new(shape, dtype or self.T)
+
+    def ws(self, n, st=0):
+        """The workspace operand of an op on stream `st` that needs n bytes."""
+        self.ws_need[st] = max(self.ws_need[st], int(n))
+        return WS2 if st else WS
+
+    def g(self, prm):
+        return _Ext(1, self.grad_off[id(prm)])
+
+    def sync(self, ops, src, dst):
+        """Stream `dst` waits for what stream `src` has been given so far."""
+        ev = self.arena.event()
+        ops.add(L.OP_SIGNAL, p=(ev,), stream=src)
+        ops.add(L.OP_WAIT, p=(ev,), stream=dst)
+
+    def unit(self, conv, bn, relu, x, hwc, res=None, pair=None):
+        """A unit over the N x H x W x C input `x` (`pair`: the pixel-pair stem's desc)."""
+        H, W, C = hwc
+        d = pair if pair is not None else _desc(self.N, H, W, C, conv)
+        return _Unit(conv, bn, relu, d, (H, W), self.T.itemsize, x, res, pair is not None)
+
+    # ---- forward
+    def _weights(self, u):
+        """u's KRSC weights (returned) and, for a backward, the dgrad's CRSK copy (u.wc)."""
+        d, conv = u.d, u.conv
+        K, k, cm = conv.out_channels, conv.kernel_size, conv.in_channels
+        wk = self.buf((K, d.R, d.S, d.C))
+        if u.pair:  # stem over pixel pairs: its own weight map, no dgrad copy
+            self.fw.add(L.OP_STEM_PAIR_PACK, i=(K, cm, k, k), p=(conv.weight, wk))
+            return wk
+        u.wc = self.buf((d.C, k, k, K)) if self.keep else None
+        if d.C == cm:  # packed by the plan's single multi-tensor pack launch (pack_at_head)
+            self.packs.append((conv.weight, wk, u.wc, K, d.C, cm, k * k))
+        else:  # channel-padded input (fp32 stem): its own pack
+            self.fw.add(L.OP_CONV_PACK, self.dt, i=(cm,), p=(conv.weight, wk, u.wc), d=d)
+        return wk
+
+    def conv_fwd(self, u, st=0):
+        """u's conv on stream `st`; returns the BN statistics its epilogue leaves:
+        (partials, slabs, rows per slab)."""
+        d = u.d
+        u.y = self.buf((d.N, d.P, d.Q, d.K))
+        nstat = L.lib().mmdx_conv_fwd_stat_blocks(d) if self.train else 0
+        part = self.buf((d.K, nstat, 2), torch.float32) if self.train else None
+        wk = self._weights(u)
+        rpb = L.lib().mmdx_conv_fwd_stat_rows(d)  # rows per statistics slab (part)
+        self.fw.timed(u.cost("fwd"), L.OP_CONV_FWD, stream=st, dtype=self.dt,
+                      i=(rpb if self.train else 0,), p=(u.x, wk, u.y, part), d=d)
+        return part, nstat, rpb
+
+    def bn_fwd(self, u, stats, out, st=0):
+        """Statistics (train: from the conv's partials), then BN(+u.res)(+ReLU) into `out`.
+        out None: the statistics only — u's consumer normalises on the fly and the
+        post-activation tensor is never written."""
+        part, nstat, rpb = stats
+        d, bn = u.d, u.bn
+        rows = d.N * d.P * d.Q
+        u.out = out
+        u.mean = self.buf((d.K,), torch.float32)
+        u.rstd = self.buf((d.K,), torch.float32)
+        # a residual unit's backward needs its ReLU mask: kept as 1 bit per element
+        # (one byte per 16-B channel vector) instead of re-reading its output
+        if self.keep and u.relu and u.res is not None and out is not None:
+            u.rmask = self.buf((rows, d.K // self.vec), torch.uint8)
+        wsn = L.lib().mmdx_bn_workspace_size(rows, d.K)
+        self.fw.add(L.OP_BN_FWD, self.dt, i=(int(self.train), d.K, nstat, int(u.relu)),
+                    l=(rows, rpb, wsn), f=(bn.momentum, bn.eps), stream=st,
+                    p=(u.y, part, bn.weight, bn.bias, bn.running_mean, bn.running_var, u.mean,
+                       u.rstd, u.res, out, self.ws(wsn, st), u.rmask))
+
+    def conv_bneval(self, u, st=0):
+        """eval forward without a backward (inference, frozen phase 1): BN on running
+        statistics (+residual)(+ReLU) applied in the conv epilogue; y is never
+        materialised and no bn_apply pass runs"""
+        d, bn = u.d, u.bn
+        u.out = self.buf((d.N, d.P, d.Q, d.K))
+        wk = self._weights(u)
+        self.fw.timed(u.cost("fwd"), L.OP_CONV_FWD_BNEVAL, stream=st, dtype=self.dt,
+                      i=(int(u.relu),), f=(bn.eps,),
+                      p=(u.x, wk, u.out, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                         u.res), d=d)
+
+    def pack_join(self):
+        """The multi-tensor weight pack (pack_at_head) runs on the side stream beside the stem
+        when the stem's weights have their own pack on the main stream; the main stream joins
+        it here, before the first conv that reads a packed weight (70 us off the critical
+        path).  A stem weight already in the multi-tensor pack: the pack stays on the main
+        stream, nothing to join."""
+        if not self.packs:
+            self.ev_pack = self.arena.event()
+            self.fw.add(L.OP_WAIT, p=(self.ev_pack,), stream=0)
+
+    def pack_at_head(self):
+        """every conv weight packed (KRSC fwd + CRSK dgrad copies) in ONE launch, first op"""
+        args = pack_multi_args(self.arena, self.packs)
+        st = 0 if self.ev_pack is None else 1
+        head = _OpList()
+        if st:  # side stream: after whatever the main stream ran before the plan
+            self.sync(head, 0, 1)
+        head.add(L.OP_CONV_PACK_MULTI, self.dt, stream=st, **args)
+        if st:
+            head.add(L.OP_SIGNAL, p=(self.ev_pack,), stream=1)
+        self.fw.prepend(head)
+
+    # ---- backward (ext: 0 = dfeats in T, 1 = gradient arena base, 2 = trunk input x0)
+    def _dconv(self, u, dout, kind, mask=None):
+        # kept for the per-launch parity test (tests/test_trunk_launches_gpu.py):
+        # the BN backward's upstream gradient and where its ReLU mask comes from
+        u.dconv = self.buf(tuple(u.y.shape))
+        u.dout, u.dout_mask, u.bwd_kind = dout, mask, kind
+        return u.dconv
+
+    def bn_bwd(self, u, dout, stats=None, want_dres=False):
+        """BN(+res)(+ReLU) backward of u.  ReLU mask: a residual unit's bit mask from the
+        forward (else its output); no residual: recomputed from y.  `stats`: u's partials
+        (buffer, tiles), already made by the dgrad that produced `dout`.  `want_dres`: the
+        residual's gradient written out too (returned)."""
+        d, bn = u.d, u.bn
+        rows = d.N * d.P * d.Q
+        dconv = self._dconv(u, dout, "res" if u.res is not None else
+                            "relu" if u.relu else "plain")
+        dres = self.buf(tuple(u.y.shape)) if want_dres else None
+        out = u.out if u.res is not None and u.rmask is None else None
+        sp, sb = stats if stats is not None else (None, 0)
+        wsn = L.lib().mmdx_bn_workspace_size(rows, d.K)
+        self.bw.add(L.OP_BN_BWD, self.dt, i=(int(self.train), d.K, int(u.relu), sb),
+                    l=(rows, wsn, sp.data_ptr() if sp is not None else 0,
+                       u.rmask.data_ptr() if u.rmask is not None else 0), f=(0.0,),
+                    p=(u.y, out, dout, bn.weight, bn.bias, u.mean, u.rstd, dconv, dres,
+                       self.g(bn.weight), self.g(bn.bias), self.ws(wsn)))
+        return dres
+
+    def bn_bwd_masked(self, u, dout, mask):
+        """a downsample BN: its upstream gradient is the residual unit's dout with that
+        unit's ReLU bit mask applied on the fly (mmdx_bn_bwd_masked_dy)"""
+        d, bn = u.d, u.bn
+        rows = d.N * d.P * d.Q
+        dconv = self._dconv(u, dout, "masked", mask)
+        wsn = L.lib().mmdx_bn_workspace_size(rows, d.K)
+        self.bw.add(L.OP_BN_BWD_MASKED_DY, self.dt, i=(int(self.train), d.K), l=(rows, wsn),
+                    f=(0.0,),
+                    p=(u.y, dout, mask, bn.weight, bn.bias, u.mean, u.rstd, dconv,
+                       self.g(bn.weight), self.g(bn.bias), self.ws(wsn)))
+
+    def bn_bwd_pool(self, u, dout, argmax, pool):
+        """`dout` is the stem pool's OUTPUT gradient: the BN backward gathers
+        dL/d(pool input) through the pool's argmax itself (mmdx_bn_bwd_pool)"""
+        pN, pH, pW, pC, pk, ps_, pp, pP, pQ = pool
+        d, bn = u.d, u.bn
+        dconv = self._dconv(u, dout, "pool")
+        wsn = L.lib().mmdx_bn_workspace_size(d.N * d.P * d.Q, d.K)
+        self.bw.add(L.OP_BN_BWD_POOL, self.dt,
+                    i=(int(self.train), pN, pH, pW, pC, int(u.relu), pP, pQ),
+                    l=(wsn, pk, ps_, pp), f=(0.0,),
+                    p=(u.y, argmax, dout, bn.weight, bn.bias, u.mean, u.rstd, dconv,
+                       self.g(bn.weight), self.g(bn.bias), self.ws(wsn)))
+
+    def bn_bwd_pair(self, u, v, dout):
+        """bn3 (u) and the downsample BN (v) read the same masked gradient — `dout` under
+        u's ReLU bit mask: one reduce, one finalize and one apply for both
+        (mmdx_bn_bwd_pair)"""
+        d = u.d
+        rows = d.N * d.P * d.Q
+        assert u.rmask is not None and tuple(v.y.shape) == tuple(u.y.shape)
+        dconv = self._dconv(u, dout, "res")
+        dconv_b = self._dconv(v, dout, "masked", u.rmask)
+        wsn = L.lib().mmdx_bn_pair_workspace_size(rows, d.K)
+        tab = (ctypes.c_void_p * 8)(*[t.data_ptr() for w in (u, v) for t in
+                                      (w.bn.weight, w.bn.bias, w.mean, w.rstd)])
+        self.arena.bufs.append(tab)  # host table the op points at: lives with the plan
+        self.bw.add(L.OP_BN_BWD_PAIR, self.dt, i=(int(self.train), d.K), l=(rows, wsn),
+                    f=(0.0,),
+                    p=(dout, u.rmask, u.y, dconv, self.g(u.bn.weight), self.g(u.bn.bias),
+                       v.y, dconv_b, self.g(v.bn.weight), self.g(v.bn.bias), self.ws(wsn),
+                       ctypes.addressof(tab)))
+
+    def wgrad(self, u):
+        """u's weight gradient on the side stream (which already waits for u's dconv)."""
+        d, cv = u.d, u.conv
+        wsn = L.lib().mmdx_conv_wgrad_workspace_size(self.dt, d)
+        x = _Ext(2) if isinstance(u.x, _Ext) else u.x
+        # pair stem: the pair-conv gradient [K][8][R][S2], then mapped to the master layout
+        dw = self.buf((d.K, d.C, d.R, d.S), torch.float32) if u.pair else self.g(cv.weight)
+        self.bw.timed(u.cost("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=self.dt,
+                      i=(d.C if u.pair else cv.in_channels,), l=(wsn,), f=(0.0,),
+                      p=(x, u.dconv, dw, self.ws(wsn, 1)), d=d)
+        if u.pair:
+            self.bw.add(L.OP_STEM_PAIR_GRAD, stream=1,
+                        i=(d.K, cv.in_channels, cv.kernel_size, cv.kernel_size), f=(0.0,),
+                        p=(dw, self.g(cv.weight)))
+
+    def wgrads_after_bn(self, *units):
+        """one event after the BN backward(s): the side stream's wgrads wait on it"""
+        self.sync(self.bw, 0, 1)
+        for u in units:
+            self.wgrad(u)
+
+    def dx_buf(self, u):
+        d = u.d
+        return self.buf((d.N, d.H, d.W, d.C))
+
+    def dgrad(self, u, dx, beta):
+        """dx = dgrad(u) + beta dx"""
+        self.bw.timed(u.cost("dgrad", u.in_bytes() if beta else 0), L.OP_CONV_DGRAD,
+                      dtype=self.dt, f=(beta,), p=(u.dconv, u.wc, dx), d=u.d)
+        u.dx = dx
+
+    def dgrad_accmask(self, u, dx, src, mask):
+        """dx = dgrad(u) + (ReLU bit ? src : 0)"""
+        xb = u.in_bytes()
+        self.bw.timed(u.cost("dgrad", xb + xb // 16), L.OP_CONV_DGRAD_ACCMASK, dtype=self.dt,
+                      p=(u.dconv, u.wc, dx, src, mask), d=u.d)
+        u.dx = dx
+
+    def dgrad_bnstat(self, u, dx, feed, tiles):
+        """dx = dgrad(u), which is `feed`'s dout: feed's BN-backward partials are made in
+        the epilogue, `tiles` per channel (returned as bn_bwd's `stats`)."""
+        d, fb = u.d, feed.bn
+        part = self.buf((d.C, tiles, 2), torch.float32)
+        self.bw.timed(u.cost("dgrad", u.in_bytes()), L.OP_CONV_DGRAD_BNSTAT, dtype=self.dt,
+                      i=(1,), f=(0.0,),
+                      p=(u.dconv, u.wc, dx, feed.y, fb.weight, fb.bias, feed.mean, feed.rstd,
+                         part, None), d=d)
+        u.dx = dx
+        return part, tiles
+
+    def finish(self):
+        """one workspace per stream for the ops of this plan (each stream runs in order)"""
+        ws = [self.buf((max(1, n),), torch.uint8) for n in self.ws_need]
+        for lst in (self.fw, self.bw):
+            if lst is not None:
+                lst.patch({WS: ws[0].data_ptr(), WS2: ws[1].data_ptr()})
+
+
+def _unit_fwd(r, u, st=0, join=None):
+    """conv + BN(+res)(+ReLU) on stream `st`; `join`: an event that stream waits for before
+    the first op that reads u.res (the downsample branch)."""
+    if r.fold:
+        if join is not None:
+            r.fw.add(L.OP_WAIT, p=(join,), stream=st)
+        r.conv_bneval(u, st)
+        return
+    stats = r.conv_fwd(u, st)
+    if join is not None:
+        r.fw.add(L.OP_WAIT, p=(join,), stream=st)
+    r.bn_fwd(u, stats, r.buf(tuple(u.y.shape)), st)
+
+
+def _record_stem(r, trunk, H, W, in_nchw, cin):
+    """Input conversion, stem conv + BN + ReLU, max pool.  Returns the trunk input operand
+    x0, the stem_pool record and the pooled tensor's (H, W, C)."""
+    N, T, fw = r.N, r.T, r.fw
+    stem_conv, bn0, mp = trunk[0], trunk[1], trunk[3]
+    # bf16: the stem runs as a conv over pixel pairs of the zero-bordered image
+    # (mmdx_stem_pair_*: K = 224, no border taps) instead of a channel-padded NHWC copy
+    ks, ss, ps = stem_conv.kernel_size, stem_conv.stride, stem_conv.padding
+    stem_pair = (in_nchw and T == torch.bfloat16 and ss == 2 and cin <= 4
+                 and stem_conv.in_channels == cin and (W + 2 * ps) % 2 == 0)
+    d_pair = None
+    if stem_pair:
+        d_pair = L.ConvDesc()
+        call("mmdx_stem_pair_desc", N, cin, H, W, stem_conv.out_channels, ks, ks, ss, ps,
+             ctypes.byref(d_pair))
+        cp = 8
+        x0 = r.buf((N, d_pair.H, d_pair.W, 8))
+        fw.add(L.OP_STEM_PAIR_INPUT, i=(N, cin, H, W, ps), p=(_Ext(0), x0))
+    elif in_nchw:
+        cp = r.vec
+        x0 = r.buf((N, H, W, cp))
+        fw.add(L.OP_NCHW2NHWC, r.dt, i=(N, cin, H, W, cp), p=(_Ext(0), x0))
+    else:
+        cp = cin
+        x0 = _Ext(0)
+    # train forward: the stem's BN + ReLU run inside the 3x3/2 pool (mmdx_maxpool_bn_fwd,
+    # bit-identical to apply-then-pool) — the 112x112x64 post-activation tensor is never
+    # written or re-read; the stem's backward recomputes its ReLU mask from the raw output
+    pool_bn = r.train and not r.fold and mp.kernel_size == 3 and mp.stride == 2
+    su = r.unit(stem_conv, bn0, True, x0, (H, W, cp), pair=d_pair)
+    if pool_bn:
+        r.bn_fwd(su, r.conv_fwd(su), None)
+    else:
+        _unit_fwd(r, su)
+    H, W, C = su.d.P, su.d.Q, su.d.K
+    P = (H + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
+    Q = (W + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
+    pooled = r.buf((N, P, Q, C))
+    am = r.buf((N, P, Q, C), torch.uint8)
+    if pool_bn:
+        fw.add(L.OP_MAXPOOL_BN_FWD, r.dt,
+               i=(N, H, W, C, mp.kernel_size, mp.stride, mp.padding, P), l=(Q, 1),
+               p=(su.y, pooled, am, bn0.weight, bn0.bias, su.mean, su.rstd))
+    else:
+        fw.add(L.OP_MAXPOOL_FWD, r.dt,
+               i=(N, H, W, C, mp.kernel_size, mp.stride, mp.padding, P),
+               l=(Q,), p=(su.out, pooled, am))
+    stem_pool = dict(u=su, argmax=am, pooled=pooled, geom=(N, H, W, C, P, Q), fused=pool_bn)
+    return x0, stem_pool, (P, Q, C)
+
+
+def _block_fwd(r, blk, x_in, hwc):
+    """One residual block over `x_in` (H, W, C = hwc).  Returns its units, its downsample
+    unit (or None), its output and the output's (H, W, C)."""
+    ds_u = ds_done = None
+    idn = x_in
+    if blk.downsample is not None:
+        ds_u = r.unit(blk.downsample[0], blk.downsample[1], False, x_in, hwc)
+        if DS_SIDE_STREAM:
+            # the downsample branch (conv + BN) runs on the side stream beside the
+            # block's conv1 / conv2 / conv3; the main stream joins it right before
+            # the residual BN apply that reads it (the side stream is idle in the
+            # forward: it carries the weight gradients in the backward)
+            r.sync(r.fw, 0, 1)
+            _unit_fwd(r, ds_u, st=1)
+            ds_done = r.arena.event()
+            r.fw.add(L.OP_SIGNAL, p=(ds_done,), stream=1)
+        else:
+            _unit_fwd(r, ds_u)
+        idn = ds_u.out
+    bu = []
+    h = x_in
+    specs = blk.units()
+    for i, (conv, bn, relu) in enumerate(specs):
+        last = i == len(specs) - 1
+        u = r.unit(conv, bn, relu, h, hwc, res=idn if last else None)
+        _unit_fwd(r, u, join=ds_done if last else None)
+        h, hwc = u.out, (u.d.P, u.d.Q, u.d.K)
+        bu.append(u)
+    return bu, ds_u, h, hwc
+
+
+def _dgrad_feeding(r, u, feed):
+    """u's dgrad into a new tensor: the gradient of unit `feed`'s output (no residual inside
+    a block), so it also makes feed's BN-backward partials where the kernel can.  Returns
+    (dx, feed's `stats` or None)."""
+    # (units with a residual are not fed: their producer is conv1's dgrad
+    # accumulating onto the identity-path gradient; the ABI supports it
+    # (beta 1, mask from the unit's output) but its heavier epilogue measured
+    # 0.8 ms/step slower than the separate reduce at C4)
+    dx = r.dx_buf(u)
+    tiles = (L.lib().mmdx_conv_dgrad_stat_blocks(r.dt, u.d)
+             if feed is not None and feed.relu else 0)
+    if tiles > 0:
+        return dx, r.dgrad_bnstat(u, dx, feed, tiles)
+    r.dgrad(u, dx, 0.0)
+    return dx, None
+
+
+def _block_bwd(r, bu, ds_u, dx, pair_on):
+    """Backward of one block from `dx`, the gradient of its output: per unit the BN backward,
+    the wgrad (side stream) and the dgrad.  Returns the gradient of the block's input."""
+    last = bu[-1]
+    # identity block (bf16, 1-bit ReLU mask kept): conv1's dgrad adds the masked
+    # block-output gradient itself, the residual unit writes no d_residual
+    # (blocks with a downsample: its BN backward reads the same masked gradient)
+    mask_id = r.T == torch.bfloat16 and len(bu) > 1 and last.rmask is not None
+    acc_id = mask_id and ds_u is None
+    # downsample block: its two BN backwards run as one paired op, issued where
+    # bn3's is, and the downsample wgrad follows conv3's on the side stream
+    paired = mask_id and ds_u is not None and pair_on
+    dres = None
+    if paired:
+        r.bn_bwd_pair(last, ds_u, dx)
+        r.wgrads_after_bn(last, ds_u)
+    else:
+        dres = r.bn_bwd(last, dx, want_dres=not mask_id)
+        r.wgrads_after_bn(last)
+    # unit i's dgrad produces the gradient of unit i-1's output (no residual
+    # inside a block): it also makes unit i-1's BN-backward partials
+    dh, fed = _dgrad_feeding(r, last, bu[-2] if len(bu) > 1 else None)
+    for k in range(len(bu) - 2, -1, -1):
+        uu = bu[k]
+        if k == 0 and ds_u is not None and not paired:
+            # the downsample BN's backward and wgrad (paired: issued with bn3's above)
+            if mask_id:
+                r.bn_bwd_masked(ds_u, dx, last.rmask)
             else:
-                o.p[j] = v  # None or int
-        if d is not None:
-            o.d = d
-        self.ops.append(o)
-
-    def timed(self, name, code, stream=0, **kw):
-        k = len(self.conv_names)
-        self.add(L.OP_EVENT, i=(2 * k,), stream=stream)
-        self.add(code, stream=stream, **kw)
-        self.add(L.OP_EVENT, i=(2 * k + 1,), stream=stream)
-        self.conv_names.append(name)
-
-    def cut(self):
-        """Segment boundary at the current end of the list: run(between=...) returns to the
-        caller here (the data-parallel hook issues a layer's all-reduce from the host
-        between two segments, with nothing but the plan's own streams)."""
-        self.cuts = getattr(self, "cuts", []) + [len(self.ops)]
-
-    def freeze(self):
-        arr = (L.PlanOp * len(self.ops))(*self.ops)
-        self.arr, self.n = arr, len(self.ops)
-        self.bounds = [0] + [c for c in getattr(self, "cuts", []) if 0 < c < self.n] + [self.n]
-        self.ops = None
-        return self
-
-    def run(self, ext, streams, between=None, timer=None):
-        """Replay the list.  between(k): called after segment k (k = 0 .. cuts-1) is
-        enqueued and before segment k+1 is; None = one native call for the whole list.
-        timer: the launch timer of the timed ops (default CONV_TIMER)."""
-        exts = (ctypes.c_void_p * max(1, len(ext)))(*ext)
-        sts = (ctypes.c_void_p * len(streams))(*streams)
-        evs = None
-        timer = CONV_TIMER if timer is None else timer
-        if getattr(timer, "active", False) and self.conv_names:
-            evs = timer.take(self.conv_names)
-            evs = (ctypes.c_void_p * len(evs))(*[e.cuda_event for e in evs])
-        if between is None or len(self.bounds) == 2:
-            call("mmdx_plan_run", self.arr, self.n, exts, evs, sts, len(streams))
-            return
-        sz = ctypes.sizeof(L.PlanOp)
-        base = ctypes.addressof(self.arr)
-        for k, (a, z) in enumerate(zip(self.bounds[:-1], self.bounds[1:])):
-            seg = ctypes.cast(base + a * sz, ctypes.POINTER(L.PlanOp))
-            call("mmdx_plan_run", seg, z - a, exts, evs, sts, len(streams))
-            if k < len(self.bounds) - 2:
-                between(k)
+                r.bn_bwd(ds_u, dres)
+            r.wgrads_after_bn(ds_u)
+        if k == 0 and ds_u is not None and ds_u.d.stride_h > 1:
+            # d(block input) = dgrad(conv1) + dgrad(strided downsample): conv1's
+            # dgrad writes it (beta 0), then the 1x1/2 downsample's dgrad adds
+            # its one output phase (beta 1; the phases no tap reaches are left
+            # alone) — instead of the downsample writing 3/4 zeros first and
+            # conv1 re-reading the whole tensor to accumulate onto it
+            r.bn_bwd(uu, dh, fed)
+            r.wgrads_after_bn(uu)
+            dh = r.dx_buf(uu)
+            r.dgrad(uu, dh, 0.0)
+            r.dgrad(ds_u, dh, 1.0)
+        elif k == 0 and acc_id:
+            r.bn_bwd(uu, dh, fed)
+            r.wgrads_after_bn(uu)
+            dh = r.dx_buf(uu)
+            r.dgrad_accmask(uu, dh, dx, last.rmask)
+        elif k == 0:
+            # d(block input) = dgrad(conv1) + identity-path grad (beta = 1)
+            if ds_u is not None:
+                dxi = r.dx_buf(ds_u)
+                r.dgrad(ds_u, dxi, 0.0)
+            else:
+                dxi = dres
+            r.bn_bwd(uu, dh, fed)
+            r.wgrads_after_bn(uu)
+            r.dgrad(uu, dxi, 1.0)
+            dh = dxi
+        else:
+            r.bn_bwd(uu, dh, fed)
+            r.wgrads_after_bn(uu)
+            dh, fed = _dgrad_feeding(r, uu, bu[k - 1])
+    return dh
 
 
-class _Arena:
-    """Buffers of one recorded forward (+ backward) of the trunk."""
+def _stem_bwd(r, mp, stem_pool, dx):
+    """Max pool, stem BN + ReLU and stem wgrad from `dx`, the pooled tensor's gradient
+    (no dgrad into the image)."""
+    su, am = stem_pool["u"], stem_pool["argmax"]
+    n0, h0, w0, c0, p0, q0 = stem_pool["geom"]
+    if mp.kernel_size == 3 and mp.stride == 2 and mp.padding <= 1 and su.relu:
+        # the pool's backward runs inside the stem BN backward: the 112x112x64
+        # gradient of the pool input is never materialised
+        r.bn_bwd_pool(su, dx, am, (n0, h0, w0, c0, mp.kernel_size, mp.stride, mp.padding,
+                                   p0, q0))
+    else:
+        da = r.buf((n0, h0, w0, c0))
+        r.bw.add(L.OP_MAXPOOL_BWD, r.dt, i=(n0, h0, w0, c0, mp.kernel_size, mp.stride,
+                                            mp.padding, p0), l=(q0,), p=(am, dx, da))
+        r.bn_bwd(su, da)
+    r.wgrads_after_bn(su)
 
-    def __init__(self):
-        self.bufs = []
-        self.owner = None  # weakref to the autograd ctx token holding the saved activations
 
-    def new(self, shape, dtype, dev):
-        t = torch.empty(shape, dtype=dtype, device=dev)
-        self.bufs.append(t)
-        return t
-
-    def event(self):
-        """A synchronisation event owned by the arena (recorded once so it exists)."""
-        e = torch.cuda.Event()
-        e.record(torch.cuda.current_stream())
-        self.bufs.append(e)
-        return e.cuda_event
-
-    def busy(self):
-        return self.owner is not None and self.owner() is not None
+def _layer_regions(trunk, grad_off, grad_bytes):
+    """Per-layer gradient regions for data parallelism.  engine_params is in forward
+    order, so layer k's gradients are one contiguous slice of the arena and layers
+    4, 3, 2 are its tail.  Returns {number of blocks (from the last) whose backward is
+    enqueued when that layer's is complete: (lo, hi) of the layer} for layers 4, 3, 2, and
+    layer 4's lo."""
+    layer_lo = []
+    for li in range(4, 8):
+        ids_ = {id(q) for q in trunk[li].parameters()}
+        layer_lo.append(min(o for i, o in grad_off.items() if i in ids_) // 4)
+    layer_hi = layer_lo[1:] + [grad_bytes // 4]
+    done_at = {}
+    acc = 0
+    for li in (3, 2, 1):           # layer4, layer3, layer2 (indices into layer_lo)
+        acc += len(trunk[li + 4])
+        done_at[acc] = (layer_lo[li], layer_hi[li])
+    return done_at, layer_lo[3]
 
 
 class _Plan:
     """Recorded forward / backward op lists of one trunk configuration (one arena)."""
 
     def __init__(self, trunk, N, H, W, in_nchw, cin, T, train, keep, dev):
-        dt = L.dtype_code(T)
-        vec = _VEC[T]
-        A = self.arena = _Arena()
-        fw = _OpList()
-        ws_need = [0, 0]  # per stream: 0 = main, 1 = weight-gradient side stream
-
-        def ws_for(n, st=0):
-            ws_need[st] = max(ws_need[st], int(n))
-
-        # ---- forward
-        stem_conv = trunk[0]
-        # bf16: the stem runs as a conv over pixel pairs of the zero-bordered image
-        # (mmdx_stem_pair_*: K = 224, no border taps) instead of a channel-padded NHWC copy
-        ks, ss, ps = stem_conv.kernel_size, stem_conv.stride, stem_conv.padding
-        stem_pair = (in_nchw and T == torch.bfloat16 and ss == 2 and cin <= 4
-                     and stem_conv.in_channels == cin and (W + 2 * ps) % 2 == 0)
-        d_pair = None
-        if stem_pair:
-            d_pair = L.ConvDesc()
-            call("mmdx_stem_pair_desc", N, cin, H, W, stem_conv.out_channels, ks, ks, ss, ps,
-                 ctypes.byref(d_pair))
-            cp = 8
-            x0 = A.new((N, d_pair.H, d_pair.W, 8), T, dev)
-            fw.add(L.OP_STEM_PAIR_INPUT, i=(N, cin, H, W, ps), p=(_Ext(0), x0))
-        elif in_nchw:
-            cp = vec
-            x0 = A.new((N, H, W, cp), T, dev)
-            fw.add(L.OP_NCHW2NHWC, dt, i=(N, cin, H, W, cp), p=(_Ext(0), x0))
-        else:
-            cp = cin
-            x0 = _Ext(0)
-        self.x0 = x0
-        units = []
-        packs = []
-        fold = not train and not keep   # eval-mode BN folded into the conv epilogue
-
-        def unit(conv, bn, relu, x, N, H, W, C, cm, res, pair=None, st=0, join=None,
-                 stats_only=False):
-            """conv + BN(+res)(+ReLU) on stream `st`; `join`: an event the main stream
-            waits for before the first op that reads `res` (the downsample branch);
-            `stats_only`: the BN's statistics only — its consumer normalises on the fly and
-            the post-activation tensor is never written (u["out"] is None)."""
-            d = pair if pair is not None else _desc(N, H, W, C, conv)
-            K, k = conv.out_channels, conv.kernel_size
-            pq = (d.P, d.Q)
-            cost = lambda kind, extra=0: conv_cost(kind, conv, N, H, W, pq[0], pq[1],  # noqa
-                                                   T.itemsize, extra)
-            y = A.new((N, d.P, d.Q, K), T, dev)
-            nstat = L.lib().mmdx_conv_fwd_stat_blocks(d) if train else 0
-            part = A.new((K, nstat, 2), torch.float32, dev) if train else None
-            wk = A.new((K, d.R, d.S, d.C), T, dev)
-            if pair is not None:  # stem over pixel pairs: its own weight map, no dgrad copy
-                wc = None
-                fw.add(L.OP_STEM_PAIR_PACK, i=(K, conv.in_channels, k, k),
-                       p=(conv.weight, wk))
-            else:
-                wc = A.new((C, k, k, K), T, dev) if keep else None
-                if C == cm:  # packed by the plan's single multi-tensor pack launch (below)
-                    packs.append((conv.weight, wk, wc, K, C, cm, k * k))
-                else:  # channel-padded input (fp32 stem): its own pack
-                    fw.add(L.OP_CONV_PACK, dt, i=(cm,), p=(conv.weight, wk, wc), d=d)
-            if fold:
-                # eval forward without a backward (inference, frozen phase 1): BN on running
-                # statistics (+residual)(+ReLU) applied in the conv epilogue; y is never
-                # materialised and no bn_apply pass runs
-                if join is not None:
-                    fw.add(L.OP_WAIT, p=(join,), stream=st)
-                fw.timed(cost("fwd"), L.OP_CONV_FWD_BNEVAL, stream=st, dtype=dt, i=(int(relu),),
-                         f=(bn.eps,),
-                         p=(x, wk, y, bn.weight, bn.bias, bn.running_mean, bn.running_var, res),
-                         d=d)
-                u = dict(conv=conv, bn=bn, relu=relu, d=d, cm=cm, x=x, y=None, out=y,
-                         mean=None, rstd=None, wc=wc, pair=pair is not None, res=res)
-                units.append(u)
-                return y, d, u
-            rpb = L.lib().mmdx_conv_fwd_stat_rows(d)  # rows per statistics slab (part)
-            out = None if stats_only else A.new((N, d.P, d.Q, K), T, dev)
-            rows = N * d.P * d.Q
-            mean = A.new((K,), torch.float32, dev)
-            rstd = A.new((K,), torch.float32, dev)
-            # a residual unit's backward needs its ReLU mask: kept as 1 bit per element
-            # (one byte per 16-B channel vector) instead of re-reading its output
-            rmask = (A.new((rows, K // vec), torch.uint8, dev)
-                     if keep and relu and res is not None and out is not None else None)
-            fw.timed(cost("fwd"), L.OP_CONV_FWD, stream=st, dtype=dt,
-                     i=(rpb if train else 0,), p=(x, wk, y, part), d=d)
-            wsn = L.lib().mmdx_bn_workspace_size(rows, K)
-            ws_for(wsn, st)
-            if join is not None:
-                fw.add(L.OP_WAIT, p=(join,), stream=st)
-            fw.add(L.OP_BN_FWD, dt, i=(int(train), K, nstat, int(relu)), l=(rows, rpb, wsn),
-                   f=(bn.momentum, bn.eps), stream=st,
-                   p=(y, part, bn.weight, bn.bias, bn.running_mean, bn.running_var, mean,
-                      rstd, res, out, _WS2 if st else _WS, rmask))
-            u = dict(conv=conv, bn=bn, relu=relu, d=d, cm=cm, x=x, y=y, out=out, mean=mean,
-                     rstd=rstd, wc=wc, pair=pair is not None, rmask=rmask, res=res, cost=cost)
-            units.append(u)
-            return out, d, u
-
-        mp = trunk[3]
-        # train forward: the stem's BN + ReLU run inside the 3x3/2 pool (mmdx_maxpool_bn_fwd,
-        # bit-identical to apply-then-pool) — the 112x112x64 post-activation tensor is never
-        # written or re-read; the stem's backward recomputes its ReLU mask from the raw output
-        pool_bn = train and not fold and mp.kernel_size == 3 and mp.stride == 2
-        a, d, stem_u = unit(stem_conv, trunk[1], True, x0, N, H, W, cp, 3, None,
-                            pair=d_pair, stats_only=pool_bn)
-        H, W, C = d.P, d.Q, d.K
-        P = (H + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
-        Q = (W + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
-        pooled = A.new((N, P, Q, C), T, dev)
-        am = A.new((N, P, Q, C), torch.uint8, dev)
-        if pool_bn:
-            bn0 = trunk[1]
-            fw.add(L.OP_MAXPOOL_BN_FWD, dt,
-                   i=(N, H, W, C, mp.kernel_size, mp.stride, mp.padding, P), l=(Q, 1),
-                   p=(stem_u["y"], pooled, am, bn0.weight, bn0.bias, stem_u["mean"],
-                      stem_u["rstd"]))
-        else:
-            fw.add(L.OP_MAXPOOL_FWD, dt,
-                   i=(N, H, W, C, mp.kernel_size, mp.stride, mp.padding, P),
-                   l=(Q,), p=(a, pooled, am))
-        stem_geom = (N, H, W, C, P, Q)
-        x_cur, H, W = pooled, P, Q
-        blocks = []
-        # the multi-tensor weight pack (below) runs on the side stream beside the stem (whose
-        # weights have their own pack on the main stream); the main stream joins it here,
-        # before the first conv that reads a packed weight (70 us off the critical path)
-        pack_side = len(packs) == 0
-        ev_pack_t = None
-        wait_pos = len(fw.ops)
-        if pack_side:
-            ev_pack_t = A.event()
-            fw.add(L.OP_WAIT, p=(ev_pack_t,), stream=0)
-        for layer in list(trunk)[4:8]:
-            for blk in layer:
-                x_in = x_cur
-                bu = []
-                h, hH, hW, hC = x_in, H, W, C
-                ds_u = None
-                ds_done = None
-                if blk.downsample is not None and not DS_SIDE_STREAM:
-                    idn, _, ds_u = unit(blk.downsample[0], blk.downsample[1], False, x_in, N, H,
-                                        W, C, C, None)
-                elif blk.downsample is not None:
-                    # the downsample branch (conv + BN) runs on the side stream beside the
-                    # block's conv1 / conv2 / conv3; the main stream joins it right before
-                    # the residual BN apply that reads it (the side stream is idle in the
-                    # forward: it carries the weight gradients in the backward)
-                    ev_in = A.event()
-                    fw.add(L.OP_SIGNAL, p=(ev_in,), stream=0)
-                    fw.add(L.OP_WAIT, p=(ev_in,), stream=1)
-                    idn, _, ds_u = unit(blk.downsample[0], blk.downsample[1], False, x_in, N, H,
-                                        W, C, C, None, st=1)
-                    ds_done = A.event()
-                    fw.add(L.OP_SIGNAL, p=(ds_done,), stream=1)
-                else:
-                    idn = x_in
-                specs = blk.units()
-                for i, (conv, bn, relu) in enumerate(specs):
-                    last = i == len(specs) - 1
-                    res = idn if last else None
-                    h, dd, uu = unit(conv, bn, relu, h, N, hH, hW, hC, hC, res,
-                                     join=ds_done if last else None)
-                    hH, hW, hC = dd.P, dd.Q, dd.K
-                    bu.append(uu)
-                blocks.append((bu, ds_u, (H, W, C)))
-                x_cur, H, W, C = h, hH, hW, hC
-        # every conv weight packed (KRSC fwd + CRSK dgrad copies) in ONE launch, first op
-        if packs:
-            items = (L.PackItem * len(packs))()
-            nb = 0
-            for j, (wm, wk, wc, K_, C_, cm_, rs) in enumerate(packs):
-                items[j] = L.PackItem(wm.data_ptr(), wk.data_ptr(),
-                                      wc.data_ptr() if wc is not None else None, K_, C_, cm_,
-                                      rs, nb)
-                nb += L.lib().mmdx_conv_pack_blocks(K_, C_, rs)
-            raw = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
-            tbl = A.new((raw.numel(),), torch.uint8, dev)
-            tbl.copy_(raw)
-            if pack_side:  # side stream: after whatever the main stream ran before the plan
-                ev_start_t = A.event()
-                fw.add(L.OP_SIGNAL, p=(ev_start_t,), stream=0)
-                fw.add(L.OP_WAIT, p=(ev_start_t,), stream=1)
-                fw.add(L.OP_CONV_PACK_MULTI, dt, i=(len(packs),), l=(nb,), p=(tbl,), stream=1)
-                fw.add(L.OP_SIGNAL, p=(ev_pack_t,), stream=1)
-                head = fw.ops[-4:]
-                del fw.ops[-4:]
-                fw.ops[0:0] = head
-            else:
-                fw.add(L.OP_CONV_PACK_MULTI, dt, i=(len(packs),), l=(nb,), p=(tbl,))
-                fw.ops.insert(0, fw.ops.pop())
-        elif pack_side:
-            del fw.ops[wait_pos]
-        self.feats = A.new((N, C), T, dev)
-        fw.add(L.OP_AVGPOOL_FWD, dt, i=(N, H * W, C), p=(x_cur, self.feats))
+        r = _Rec(trunk, N, T, train, keep, dev)
+        self.arena = r.arena
+        self.x0, self.stem_pool, hwc = _record_stem(r, trunk, H, W, in_nchw, cin)
+        x = self.stem_pool["pooled"]
+        blks = [b for layer in list(trunk)[4:8] for b in layer]
+        if blks:  # (every block conv's weights go through the multi-tensor pack)
+            r.pack_join()
+        # the recorded blocks and stem pool buffers are read by the per-launch parity test
+        self.blocks = []
+        for blk in blks:
+            bu, ds_u, y, hwc_out = _block_fwd(r, blk, x, hwc)
+            self.blocks.append((bu, ds_u, hwc))
+            x, hwc = y, hwc_out
+        if r.packs:
+            r.pack_at_head()
+        H, W, C = hwc
+        self.feats = r.buf((N, C))
+        r.fw.add(L.OP_AVGPOOL_FWD, r.dt, i=(N, H * W, C), p=(x, self.feats))
         self.out_geom = (N, H, W, C)
-
-        # ---- backward (ext: 0 = dfeats in T, 1 = gradient arena base, 2 = trunk input x0)
-        # The weight gradients (wgrad) run on a side stream: they depend on the BN backward
-        # of their unit but nothing on the critical dgrad chain depends on them, so they fill
-        # the CUs the chain's smaller launches leave idle.  The main stream joins the side
-        # stream once at the end, before the optimizer reads the gradients.
         self.bwd = None
-        self.tail_event = None
         self.grad_regions = []
         if keep:
-            bw = _OpList()
-            params = trunk.engine_params()
-            self.grad_off = {}
-            off = 0
-            for prm in params:
-                self.grad_off[id(prm)] = off
-                off += (prm.numel() * 4 + 15) // 16 * 16  # 16-B aligned, dense for ResNets
-            self.grad_bytes = off
-            self.params = params
-
-            def g(prm):
-                return _Ext(1, self.grad_off[id(prm)])
-
-            def xref(x):
-                return _Ext(2) if isinstance(x, _Ext) else x
-
-            def bwd_fields(u, dout, dout_mask, kind):
-                # kept for the per-launch parity test (tests/test_trunk_launches_gpu.py):
-                # the BN backward's upstream gradient and where its ReLU mask comes from
-                u["dconv"] = A.new(tuple(u["y"].shape), T, dev)
-                u["dout"], u["dout_mask"], u["bwd_kind"] = dout, dout_mask, kind
-                return u["dconv"]
-
-            def wgrad(u):
-                """u's weight gradient on the side stream (which already waits for u's dconv)."""
-                d, cv, dconv = u["d"], u["conv"], u["dconv"]
-                wsn = L.lib().mmdx_conv_wgrad_workspace_size(dt, d)
-                ws_for(wsn, 1)
-                if u["pair"]:  # pair-conv gradient [K][8][R][S2], mapped to the master layout
-                    dwp = A.new((d.K, d.C, d.R, d.S), torch.float32, dev)
-                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt, i=(d.C,),
-                             l=(wsn,),
-                             f=(0.0,), p=(xref(u["x"]), dconv, dwp, _WS2), d=d)
-                    bw.add(L.OP_STEM_PAIR_GRAD, stream=1,
-                           i=(d.K, cv.in_channels, cv.kernel_size, cv.kernel_size), f=(0.0,),
-                           p=(dwp, g(cv.weight)))
-                else:
-                    bw.timed(u["cost"]("wgrad"), L.OP_CONV_WGRAD, stream=1, dtype=dt,
-                             i=(u["cm"],),
-                             l=(wsn,), f=(0.0,), p=(xref(u["x"]), dconv, g(cv.weight), _WS2),
-                             d=d)
-
-            def unit_bwd(u, dout, want_dx, dx_acc=None, want_res=False, stats=None,
-                         feed=None, pool=None, no_dres=False, acc=None, dout_mask=None,
-                         pair_ds=None, bn_done=False):
-                """BN(+res)(+ReLU) backward, wgrad (side stream), dgrad.  `stats`: this
-                unit's BN-backward partials, already made by the dgrad that produced `dout`;
-                `feed`: the unit whose dout this unit's dgrad produces (no residual) — its
-                partials are then made in the dgrad epilogue and returned.  `pair_ds`: the
-                block's downsample unit, whose BN backward (upstream gradient: `dout` under
-                this unit's ReLU bit mask) and wgrad are issued here with this unit's
-                (mmdx_bn_bwd_pair); its later call passes `bn_done` and adds the dgrad only."""
-                d = u["d"]
-                K = d.K
-                rows = d.N * d.P * d.Q
-                if bn_done:
-                    dconv = u["dconv"]
-                else:
-                    dconv = bwd_fields(u, dout, dout_mask,
-                                       "masked" if dout_mask is not None else
-                                       "pool" if pool is not None else
-                                       "res" if want_res else "relu" if u["relu"] else "plain")
-                # no_dres: the identity path's gradient is added by conv1's dgrad epilogue
-                # from (dout, ReLU bit mask) instead (mmdx_conv_dgrad_accmask)
-                dres = (A.new(tuple(u["y"].shape), T, dev)
-                        if want_res and not no_dres and not bn_done else None)
-                wsn = L.lib().mmdx_bn_workspace_size(rows, K)
-                ws_for(wsn)
-                # ReLU mask: a residual unit's bit mask from the forward (else its output);
-                # no residual: recomputed from y
-                rmask = u.get("rmask") if want_res else None
-                out = u["out"] if want_res and rmask is None else None
-                sp, sb = stats if stats is not None else (None, 0)
-                if bn_done:
-                    pass
-                elif pair_ds is not None:
-                    # bn3 and the downsample BN read the same masked gradient: one reduce, one
-                    # finalize and one apply for both (mmdx_bn_bwd_pair)
-                    v = pair_ds
-                    assert rmask is not None and dres is None and sp is None
-                    assert tuple(v["y"].shape) == tuple(u["y"].shape)
-                    dconv_b = bwd_fields(v, dout, rmask, "masked")
-                    wsn = L.lib().mmdx_bn_pair_workspace_size(rows, K)
-                    ws_for(wsn)
-                    tab = (ctypes.c_void_p * 8)(*[t.data_ptr() for w in (u, v) for t in
-                                                  (w["bn"].weight, w["bn"].bias, w["mean"],
-                                                   w["rstd"])])
-                    A.bufs.append(tab)  # host table the op points at: lives with the plan
-                    bw.add(L.OP_BN_BWD_PAIR, dt, i=(int(train), K), l=(rows, wsn), f=(0.0,),
-                           p=(dout, rmask, u["y"], dconv, g(u["bn"].weight), g(u["bn"].bias),
-                              v["y"], dconv_b, g(v["bn"].weight), g(v["bn"].bias), _WS,
-                              ctypes.addressof(tab)))
-                elif dout_mask is not None:
-                    # a downsample BN: its upstream gradient is the residual unit's dout with
-                    # that unit's ReLU bit mask applied on the fly (mmdx_bn_bwd_masked_dy)
-                    bw.add(L.OP_BN_BWD_MASKED_DY, dt, i=(int(train), K), l=(rows, wsn),
-                           f=(0.0,),
-                           p=(u["y"], dout, dout_mask, u["bn"].weight, u["bn"].bias, u["mean"],
-                              u["rstd"], dconv, g(u["bn"].weight), g(u["bn"].bias), _WS))
-                elif pool is not None:
-                    # `dout` is the stem pool's OUTPUT gradient: the BN backward gathers
-                    # dL/d(pool input) through the pool's argmax itself (mmdx_bn_bwd_pool)
-                    am_, (pN, pH, pW, pC, pk, ps_, pp, pP, pQ) = pool
-                    bw.add(L.OP_BN_BWD_POOL, dt,
-                           i=(int(train), pN, pH, pW, pC, int(u["relu"]), pP, pQ),
-                           l=(wsn, pk, ps_, pp), f=(0.0,),
-                           p=(u["y"], am_, dout, u["bn"].weight, u["bn"].bias, u["mean"],
-                              u["rstd"], dconv, g(u["bn"].weight), g(u["bn"].bias), _WS))
-                else:
-                    bw.add(L.OP_BN_BWD, dt, i=(int(train), K, int(u["relu"]), sb),
-                           l=(rows, wsn, sp.data_ptr() if sp is not None else 0,
-                              rmask.data_ptr() if rmask is not None else 0), f=(0.0,),
-                           p=(u["y"], out, dout, u["bn"].weight, u["bn"].bias, u["mean"],
-                              u["rstd"], dconv, dres, g(u["bn"].weight), g(u["bn"].bias),
-                              _WS))
-                if not bn_done:
-                    # one event after the BN backward(s): the side stream's wgrads wait on it
-                    ev = A.event()
-                    bw.add(L.OP_SIGNAL, p=(ev,), stream=0)
-                    bw.add(L.OP_WAIT, p=(ev,), stream=1)
-                    wgrad(u)
-                    if pair_ds is not None:
-                        wgrad(pair_ds)
-                dx, fed = None, None
-                if want_dx:
-                    if dx_acc is not None:
-                        dx, beta = dx_acc, 1.0
-                    else:
-                        dx, beta = A.new((d.N, d.H, d.W, d.C), T, dev), 0.0
-                    # (units with a residual are not fed: their producer is conv1's dgrad
-                    # accumulating onto the identity-path gradient; the ABI supports it
-                    # (beta 1, mask from the unit's output) but its heavier epilogue measured
-                    # 0.8 ms/step slower than the separate reduce at C4)
-                    tiles = (L.lib().mmdx_conv_dgrad_stat_blocks(dt, d)
-                             if feed is not None and beta == 0.0 and feed["relu"] else 0)
-                    if acc is not None:  # dx = dgrad + (ReLU bit ? acc_src : 0)
-                        xb = d.N * d.H * d.W * d.C * T.itemsize
-                        bw.timed(u["cost"]("dgrad", xb + xb // 16), L.OP_CONV_DGRAD_ACCMASK,
-                                 dtype=dt,
-                                 p=(dconv, u["wc"], dx, acc[0], acc[1]), d=d)
-                    elif tiles > 0:
-                        fed = (A.new((d.C, tiles, 2), torch.float32, dev), tiles)
-                        fb = feed["bn"]
-                        bw.timed(u["cost"]("dgrad", d.N * d.H * d.W * d.C * T.itemsize),
-                                 L.OP_CONV_DGRAD_BNSTAT, dtype=dt, i=(1,), f=(0.0,),
-                                 p=(dconv, u["wc"], dx, feed["y"], fb.weight, fb.bias,
-                                    feed["mean"], feed["rstd"], fed[0], None), d=d)
-                    else:
-                        xb = d.N * d.H * d.W * d.C * T.itemsize if beta else 0
-                        bw.timed(u["cost"]("dgrad", xb), L.OP_CONV_DGRAD, dtype=dt,
-                                 f=(beta,), p=(dconv, u["wc"], dx), d=d)
-                u["dx"] = dx
-                return dx, dres, fed
-
-            # MMDX_BN_BWD_PAIR=0: the two separate BN backwards (A/B runs)
-            pair_on = bool(L.lib().mmdx_bn_bwd_pair_enabled())
-            N_, H_, W_, C_ = self.out_geom
-            dx = A.new((N_, H_, W_, C_), T, dev)
-            self.dtop = dx
-            bw.add(L.OP_AVGPOOL_BWD, dt, i=(N_, H_ * W_, C_), p=(_Ext(0), dx))
-            # Per-layer gradient regions for data parallelism.  engine_params is in forward
-            # order, so layer k's gradients are one contiguous slice of the arena and layers
-            # 4, 3, 2 are its tail.  A layer's gradients are final once the side stream has
-            # run that layer's weight gradients (each waits for its unit's BN backward, which
-            # also writes the BN parameter gradients on the main stream): the plan signals
-            # one event on the side stream right after each layer's last wgrad, so the
-            # all-reduce of layer 4 runs beside layers 3..1's backward, layer 3's beside
-            # layers 2..1's, and so on.  The stem + layer 1 (the arena's head) are reduced
-            # after the backward.  self.grad_regions: [(lo, hi, event)] in backward order.
-            layer_lo = []
-            for li in range(4, 8):
-                ids_ = {id(q) for q in trunk[li].parameters()}
-                layer_lo.append(min(o for i, o in self.grad_off.items() if i in ids_) // 4)
-            layer_hi = layer_lo[1:] + [self.grad_bytes // 4]
-            n_blocks = [len(list(trunk[li])) for li in range(4, 8)]
-            # block index (reversed order) at which layer li's backward is fully enqueued
-            done_at = {}
-            acc = 0
-            for li in (3, 2, 1):           # layer4, layer3, layer2 (indices into layer_lo)
-                acc += n_blocks[li]
-                done_at[acc] = li
-            self.grad_regions = []
-            self.grad_tail = layer_lo[3]
-            self.tail_event = None
-            for bi, (bu, ds_u, _shape) in enumerate(reversed(blocks)):
-                if bi in done_at:
-                    li = done_at[bi]
-                    bw.add(L.OP_SIGNAL, p=(A.event(),), stream=1)
-                    bw.cut()  # TRUNK_SEGMENT_HOOK runs here (region k = segment k)
-                    self.grad_regions.append((layer_lo[li], layer_hi[li], A.bufs[-1]))
-                    if li == 3:
-                        self.tail_event = A.bufs[-1]
-                # unit i's dgrad produces the gradient of unit i-1's output (no residual
-                # inside a block): it also makes unit i-1's BN-backward partials
-                # identity block (bf16, 1-bit ReLU mask kept): conv1's dgrad adds the masked
-                # block-output gradient itself, the residual unit writes no d_residual
-                # (blocks with a downsample: its BN backward reads the same masked gradient)
-                mask_id = (T == torch.bfloat16 and len(bu) > 1
-                           and bu[-1].get("rmask") is not None)
-                acc_id = mask_id and ds_u is None
-                # downsample block: its two BN backwards run as one paired op, issued where
-                # bn3's is, and the downsample wgrad follows conv3's on the side stream
-                paired = mask_id and ds_u is not None and pair_on
-                dh, dres, fed = unit_bwd(bu[-1], dx, True, want_res=True,
-                                         feed=bu[-2] if len(bu) > 1 else None,
-                                         no_dres=mask_id, pair_ds=ds_u if paired else None)
-                blk_dout = dx
-                ds_in = (dict(bn_done=True) if paired else
-                         dict(dout_mask=bu[-1]["rmask"]) if mask_id else {})
-                ds_dout = blk_dout if mask_id else dres
-                for k in range(len(bu) - 2, -1, -1):
-                    uu = bu[k]
-                    if k == 0 and ds_u is not None and ds_u["d"].stride_h > 1:
-                        # d(block input) = dgrad(conv1) + dgrad(strided downsample): conv1's
-                        # dgrad writes it (beta 0), then the 1x1/2 downsample's dgrad adds
-                        # its one output phase (beta 1; the phases no tap reaches are left
-                        # alone) — instead of the downsample writing 3/4 zeros first and
-                        # conv1 re-reading the whole tensor to accumulate onto it
-                        unit_bwd(ds_u, ds_dout, False, **ds_in)
-                        dh, _, _ = unit_bwd(uu, dh, True, stats=fed)
-                        dd_ = ds_u["d"]
-                        bw.timed(ds_u["cost"]("dgrad", dd_.N * dd_.H * dd_.W * dd_.C
-                                              * T.itemsize), L.OP_CONV_DGRAD, dtype=dt,
-                                 f=(1.0,), p=(ds_u["dconv"], ds_u["wc"], dh), d=dd_)
-                    elif k == 0 and acc_id:
-                        dh, _, _ = unit_bwd(uu, dh, True, stats=fed,
-                                            acc=(blk_dout, bu[-1]["rmask"]))
-                    elif k == 0:
-                        # d(block input) = dgrad(conv1) + identity-path grad (beta = 1)
-                        if ds_u is not None:
-                            dxi, _, _ = unit_bwd(ds_u, ds_dout, True, **ds_in)
-                        else:
-                            dxi = dres
-                        dh, _, _ = unit_bwd(uu, dh, True, dx_acc=dxi, stats=fed)
-                    else:
-                        dh, _, fed = unit_bwd(uu, dh, True, stats=fed, feed=bu[k - 1])
-                dx = dh
-            n0, h0, w0, c0, p0, q0 = stem_geom
-            if mp.kernel_size == 3 and mp.stride == 2 and mp.padding <= 1 and stem_u["relu"]:
-                # the pool's backward runs inside the stem BN backward: the 112x112x64
-                # gradient of the pool input is never materialised
-                unit_bwd(stem_u, dx, False, pool=(am, (n0, h0, w0, c0, mp.kernel_size,
-                                                       mp.stride, mp.padding, p0, q0)))
-            else:
-                da = A.new((n0, h0, w0, c0), T, dev)
-                bw.add(L.OP_MAXPOOL_BWD, dt, i=(n0, h0, w0, c0, mp.kernel_size, mp.stride,
-                                                mp.padding, p0), l=(q0,), p=(am, dx, da))
-                unit_bwd(stem_u, da, False)  # (no dgrad into the image)
-            ev = A.event()
-            bw.add(L.OP_SIGNAL, p=(ev,), stream=1)
-            bw.add(L.OP_WAIT, p=(ev,), stream=0)
-            self.bwd = bw
-        # one workspace per stream for the ops of this plan (each stream runs in order)
-        ws = [A.new((max(1, n),), torch.uint8, dev) for n in ws_need]
-        for lst in (fw,) + ((self.bwd,) if self.bwd is not None else ()):
-            for o in lst.ops:
-                for j in range(12):
-                    if o.ext[j] == -1 and o.p[j] in (_WS_TOKEN, _WS2_TOKEN):
-                        o.p[j] = ws[0 if o.p[j] == _WS_TOKEN else 1].data_ptr()
-        # the recorded units, blocks and stem pool buffers (read by the per-launch parity test)
-        self.units, self.blocks = units, blocks
-        self.stem_pool = dict(u=stem_u, argmax=am, pooled=pooled, geom=stem_geom, fused=pool_bn)
-        self.fwd = fw.freeze()
+            self.params = trunk.engine_params()
+            self.grad_off, self.grad_bytes = r.grad_off, r.grad_bytes
+            self._record_bwd(r, trunk)
+        r.finish()
+        self.fwd = r.fw.freeze()
         if self.bwd is not None:
             self.bwd.freeze()
+
+    def _record_bwd(self, r, trunk):
+        """The weight gradients (wgrad) run on a side stream: they depend on the BN backward
+        of their unit but nothing on the critical dgrad chain depends on them, so they fill
+        the CUs the chain's smaller launches leave idle.  The main stream joins the side
+        stream once at the end, before the optimizer reads the gradients."""
+        bw = self.bwd = r.bw
+        # MMDX_BN_BWD_PAIR=0: the two separate BN backwards (A/B runs)
+        pair_on = bool(L.lib().mmdx_bn_bwd_pair_enabled())
+        N, H, W, C = self.out_geom
+        dx = self.dtop = r.buf((N, H, W, C))
+        bw.add(L.OP_AVGPOOL_BWD, r.dt, i=(N, H * W, C), p=(_Ext(0), dx))
+        # A layer's gradients (_layer_regions) are final once the side stream has
+        # run that layer's weight gradients (each waits for its unit's BN backward, which
+        # also writes the BN parameter gradients on the main stream): the plan signals
+        # one event on the side stream right after each layer's last wgrad, so the
+        # all-reduce of layer 4 runs beside layers 3..1's backward, layer 3's beside
+        # layers 2..1's, and so on.  The stem + layer 1 (the arena's head) are reduced
+        # after the backward.  self.grad_regions: [(lo, hi, event)] in backward order.
+        done_at, self.grad_tail = _layer_regions(trunk, self.grad_off, self.grad_bytes)
+        for bi, (bu, ds_u, _shape) in enumerate(reversed(self.blocks)):
+            if bi in done_at:
+                bw.add(L.OP_SIGNAL, p=(r.arena.event(),), stream=1)
+                bw.cut()  # TRUNK_SEGMENT_HOOK runs here (region k = segment k)
+                self.grad_regions.append((*done_at[bi], r.arena.bufs[-1]))
+            dx = _block_bwd(r, bu, ds_u, dx, pair_on)
+        _stem_bwd(r, trunk[3], self.stem_pool, dx)
+        r.sync(bw, 1, 0)
 
 
 # TRUNK_GRAD_HOOK(grads, regions): called right after the trunk backward is enqueued with the
@@ -827,11 +826,6 @@ TRUNK_SEGMENT_HOOK = None
 # Downsample branch of the forward on the side stream (False: in order on the main stream;
 # read when a plan is built — for A/B runs, tools/step_probe.py --ds-main).
 DS_SIDE_STREAM = True
-
-# placeholder operands for the plan's per-stream workspaces, patched once sizes are known
-_WS_TOKEN, _WS2_TOKEN = 0x1, 0x2
-_WS, _WS2 = _WS_TOKEN, _WS2_TOKEN
-
 
 # MMDX_WGRAD_CUS=n: the weight-gradient stream confined to n evenly spread compute units
 # (mmdx_stream_create, a CU-masked HIP stream), leaving the rest to the dgrad / BN chain on
@@ -871,35 +865,10 @@ def _side_stream(trunk, dev):
     return st
 
 
-# recorded configurations kept per module; older keys (another batch shape, re-allocated
-# parameters) whose arenas are all idle are dropped, so their buffers can be freed
-MAX_PLAN_KEYS = 4
-
-
 def _plans_for(trunk, key, build):
     """A free arena for `key` (recording a new one if every recorded arena is held)."""
     cache = trunk.__dict__.setdefault("_mmdx_plans", {})
     return plan_cache_get(cache, key, build)
-
-
-def plan_cache_get(cache, key, build):
-    """Shared by the trunk and the encoder-stack plans: an idle plan recorded for `key`, or a
-    new one; least recently used keys beyond MAX_PLAN_KEYS are evicted when idle."""
-    lst = cache.pop(key, [])
-    cache[key] = lst   # most recently used last
-    for old in [k for k in cache if k != key][:max(0, len(cache) - MAX_PLAN_KEYS)]:
-        if not any(pl.arena.busy() for pl in cache[old]):
-            del cache[old]
-    for pl in lst:
-        if not pl.arena.busy():
-            return pl
-    pl = build()
-    lst.append(pl)
-    return pl
-
-
-class _Token:
-    pass
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -925,7 +894,8 @@ class _TrunkFn(torch.autograd.Function):
         plan = _plans_for(trunk, key,
                           lambda: _Plan(trunk, N, H, W, in_nchw, cin, T, train, keep, dev))
         # the downsample branches run on the side stream (joined inside the plan)
-        plan.fwd.run([x.data_ptr()], [stream(), _side_stream(trunk, dev).cuda_stream])
+        plan.fwd.run([x.data_ptr()], [stream(), _side_stream(trunk, dev).cuda_stream],
+                     timer=CONV_TIMER)
         if train:  # every BN's num_batches_tracked += 1, in one multi-tensor launch
             torch._foreach_add_([m.num_batches_tracked for m in trunk.modules()
                                  if isinstance(m, BatchNorm2d)], 1)
@@ -961,7 +931,7 @@ class _TrunkFn(torch.autograd.Function):
                 with torch.cuda.stream(side):
                     seg_hook(grads, lo, hi)
         plan.bwd.run([dfeats.data_ptr(), grads.data_ptr(), x0], [stream(), side.cuda_stream],
-                     between=between)
+                     timer=CONV_TIMER, between=between)
         hook = TRUNK_GRAD_HOOK
         if between is None and hook is not None and plan.grad_regions:
             hook(grads, plan.grad_regions)

@@ -27,9 +27,8 @@ import torch
 
 from . import _lib as L
 from . import functional as F
-from .resnet import _Arena, _Ext, _OpList, _Token, plan_cache_get
+from .plan import WS, _Arena, _Ext, _OpList, _Token, pack_multi_args, plan_cache_get
 
-_WS_TOKEN = 0x1   # placeholder operand for the plan's workspace (patched when sized)
 # ViT backward: residual-branch gradient added inside the LayerNorm backward (1, default) or
 # by a separate add pass (0); read by vit.py's eager path too
 VIT_LN_ADDIN = os.environ.get("MMDX_VIT_LN_ADDIN", "1") == "1"
@@ -44,17 +43,17 @@ def enabled() -> bool:
 class _Rec:
     """Records C-ABI calls as plan ops; buffers come from the plan's arena."""
 
-    def __init__(self, arena, dev, T, ops):
-        self.arena, self.dev, self.T, self.ops = arena, dev, T, ops
+    def __init__(self, arena, T, ops):
+        self.arena, self.T, self.ops = arena, T, ops
         self.dt = L.dtype_code(T)
         self.ws_need = 0
 
     def buf(self, shape, dtype=None):
-        return self.arena.new(shape, dtype or self.T, self.dev)
+        return self.arena.new(shape, dtype or self.T)
 
     def _ws(self, n):
         self.ws_need = max(self.ws_need, int(n))
-        return _WS_TOKEN if n > 0 else None
+        return WS if n > 0 else None
 
     def cast(self, src, dst):
         self.ops.add(L.OP_CAST, L.dtype_code(dst.dtype), i=(L.dtype_code(src.dtype),),
@@ -63,23 +62,16 @@ class _Rec:
     def cast_weight(self, w, dst):
         """fp32 [K][C] master -> compute-dtype copy; every one of the stack's is cast by ONE
         multi-tensor launch at the head of the forward (flush_weight_casts)."""
-        self.packs = getattr(self, "packs", []) + [(w, dst)]
+        K, Cc = w.shape[0], w.numel() // w.shape[0]
+        self.packs = getattr(self, "packs", []) + [(w, dst, None, K, Cc, Cc, 1)]
 
     def flush_weight_casts(self):
         packs = getattr(self, "packs", [])
         if not packs:
             return
-        items = (L.PackItem * len(packs))()
-        nb = 0
-        for j, (w, dst) in enumerate(packs):
-            K, Cc = w.shape[0], w.numel() // w.shape[0]
-            items[j] = L.PackItem(w.data_ptr(), dst.data_ptr(), None, K, Cc, Cc, 1, nb)
-            nb += L.lib().mmdx_conv_pack_blocks(K, Cc, 1)
-        raw = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
-        tbl = self.buf((raw.numel(),), torch.uint8)
-        tbl.copy_(raw)
-        self.ops.add(L.OP_CONV_PACK_MULTI, self.dt, i=(len(packs),), l=(nb,), p=(tbl,))
-        self.ops.ops.insert(0, self.ops.ops.pop())
+        head = _OpList()
+        head.add(L.OP_CONV_PACK_MULTI, self.dt, **pack_multi_args(self.arena, packs))
+        self.ops.prepend(head)
 
     def copy(self, src, dst, n):
         self.ops.add(L.OP_CAST, self.dt, i=(self.dt,), l=(n,), p=(src, dst))
@@ -191,8 +183,8 @@ class _StackPlan:
     """Forward + backward op lists of one stack configuration over one arena."""
 
     def __init__(self, dev, T):
-        self.arena = _Arena()
-        self.dev, self.T = dev, T
+        self.arena = _Arena(dev)
+        self.T = T
         self.fwd = _OpList()
         self.bwd = _OpList()
         self.out = None
@@ -214,12 +206,9 @@ class _StackPlan:
 
     def finish(self, recs):
         need = max(r.ws_need for r in recs)
-        ws = self.arena.new((max(1, need),), torch.uint8, self.dev)
+        ws = self.arena.new((max(1, need),), torch.uint8)
         for lst in (self.fwd, self.bwd):
-            for o in lst.ops:
-                for j in range(12):
-                    if o.ext[j] == -1 and o.p[j] == _WS_TOKEN:
-                        o.p[j] = ws.data_ptr()
+            lst.patch({WS: ws.data_ptr()})
             lst.freeze()
 
 
@@ -256,7 +245,7 @@ def _build_bert(params, B, Ls, D, Hn, I, eps, p, pa, T, dev):
     scale = 1.0 / math.sqrt(D // Hn)
     counter = L.rng_counter(dev)
     nl = len(params) // _BERT_NP
-    rf = _Rec(pl.arena, dev, T, pl.fwd)
+    rf = _Rec(pl.arena, T, pl.fwd)
     x = _Ext(0)
     mask = _Ext(1)
     saves = []
@@ -314,7 +303,7 @@ def _build_bert(params, B, Ls, D, Hn, I, eps, p, pa, T, dev):
 
     # backward: ext 0 = upstream gradient [M, D] (compute dtype), 1 = gradient buffer,
     # 2 = mask.  Shared temporaries across layers; Y carries d(layer output) downward.
-    rb = _Rec(pl.arena, dev, T, pl.bwd)
+    rb = _Rec(pl.arena, T, pl.bwd)
     mask = _Ext(2)
     X, Y = rb.buf((M, D)), rb.buf((M, D))
     DX2 = rb.buf((M, D)) if p > 0 else None
@@ -387,7 +376,7 @@ def _build_vit(params, N, S, D, heads, I, eps, T, dev):
     M = N * S
     scale = 1.0 / math.sqrt(D // heads)
     nl = len(params) // _VIT_NP
-    rf = _Rec(pl.arena, dev, T, pl.fwd)
+    rf = _Rec(pl.arena, T, pl.fwd)
     x = _Ext(0)
     saves = []
     for li in range(nl):
@@ -425,7 +414,7 @@ def _build_vit(params, N, S, D, heads, I, eps, T, dev):
     rf.flush_weight_casts()
 
     # backward: ext 0 = upstream gradient, 1 = gradient buffer, 3 = the stack input
-    rb = _Rec(pl.arena, dev, T, pl.bwd)
+    rb = _Rec(pl.arena, T, pl.bwd)
     dpre = rb.buf((M, I))
     du2, DA, da_ln = rb.buf((M, D)), rb.buf((M, D)), rb.buf((M, D))
     datt, dqkv, du1 = rb.buf((M, D)), rb.buf((M, 3 * D)), rb.buf((M, D))

@@ -83,60 +83,60 @@ def _conv_refs(x, w, dy, stride, pad):
 def _bn_fwd_checks(rep, tag, u, ref, res_ref=None):
     """Batch statistics (from the conv epilogue's fp32 slabs) against the float64 conv
     output; the apply pass (+residual)(+ReLU) and its 1-bit mask against the stored y."""
-    bn = u["bn"]
+    bn = u.bn
     y_ref = ref["y"]
     mean_ref = y_ref.mean((0, 2, 3))
     var_ref = y_ref.var((0, 2, 3), unbiased=False)
     acc_mean = ACC * ref["y_acc"].mean((0, 2, 3)) + 1e-6 * y_ref.abs().mean((0, 2, 3))
-    rep.check(f"bnstat-mean {tag}", u["mean"], mean_ref, acc_mean)
+    rep.check(f"bnstat-mean {tag}", u.mean, mean_ref, acc_mean)
     rstd_ref = (var_ref + bn.eps).rsqrt()
-    rep.check(f"bnstat-rstd {tag}", u["rstd"], rstd_ref, 1e-4 * rstd_ref)
-    if u["out"] is None:
+    rep.check(f"bnstat-rstd {tag}", u.rstd, rstd_ref, 1e-4 * rstd_ref)
+    if u.out is None:
         return
-    y = _nchw(u["y"])
+    y = _nchw(u.y)
     g = bn.weight.detach().double().view(1, -1, 1, 1)
     b = bn.bias.detach().double().view(1, -1, 1, 1)
-    m = u["mean"].double().view(1, -1, 1, 1)
-    rs = u["rstd"].double().view(1, -1, 1, 1)
+    m = u.mean.double().view(1, -1, 1, 1)
+    rs = u.rstd.double().view(1, -1, 1, 1)
     pre = (y - m) * rs * g + b
     mag = (y.abs() + m.abs()) * (rs * g).abs() + b.abs()   # fp32 y*scale + shift magnitudes
-    if u["res"] is not None:
-        r = _nchw(u["res"])
+    if u.res is not None:
+        r = _nchw(u.res)
         pre = pre + r
         mag = mag + r.abs()
-    out_ref = pre.clamp(min=0) if u["relu"] else pre
-    got = _nchw(u["out"])
+    out_ref = pre.clamp(min=0) if u.relu else pre
+    got = _nchw(u.out)
     rep.check(f"bn-apply {tag}", got, out_ref, U * out_ref.abs() + 1e-6 * mag)
-    if u.get("rmask") is not None:
-        N, P, Q, K = u["out"].shape
-        assert torch.equal(_bits(u["rmask"], (N, P, Q, K)), got > 0), f"relu bit mask {tag}"
+    if u.rmask is not None:
+        N, P, Q, K = u.out.shape
+        assert torch.equal(_bits(u.rmask, (N, P, Q, K)), got > 0), f"relu bit mask {tag}"
 
 
 def _bn_bwd_checks(rep, tag, u, plan, grads):
     """dconv (the BN backward's output, which the wgrad / dgrad launches read) and the BN
     gamma / beta gradients, from the unit's upstream gradient and its ReLU-mask source."""
-    bn = u["bn"]
-    y = _nchw(u["y"])
+    bn = u.bn
+    y = _nchw(u.y)
     N, C = y.shape[0], y.shape[1]
     M = y.numel() // C
     gam = bn.weight.detach().double().view(1, -1, 1, 1)
     bet = bn.bias.detach().double().view(1, -1, 1, 1)
-    m = u["mean"].double().view(1, -1, 1, 1)
-    rs = u["rstd"].double().view(1, -1, 1, 1)
+    m = u.mean.double().view(1, -1, 1, 1)
+    rs = u.rstd.double().view(1, -1, 1, 1)
     xh = (y - m) * rs
     pre = xh * gam + bet
-    kind = u["bwd_kind"]
+    kind = u.bwd_kind
     skip = None
     extra = 0.0
     if kind == "res":
-        g = _nchw(u["dout"]) * (_nchw(u["out"]) > 0)
+        g = _nchw(u.dout) * (_nchw(u.out) > 0)
     elif kind == "masked":
-        g = _nchw(u["dout"]) * _bits(u["dout_mask"], tuple(u["dout"].shape))
+        g = _nchw(u.dout) * _bits(u.dout_mask, tuple(u.dout.shape))
     elif kind in ("relu", "pool"):
         if kind == "pool":
             sp = plan.stem_pool
             n0, h0, w0, c0, p0, q0 = sp["geom"]
-            dp = _nchw(u["dout"])
+            dp = _nchw(u.dout)
             am = sp["argmax"].permute(0, 3, 1, 2).long()
             G = torch.zeros(n0, c0, h0 + 2, w0 + 2, dtype=torch.float64, device=y.device)
             for k in range(9):
@@ -146,13 +146,13 @@ def _bn_bwd_checks(rep, tag, u, plan, grads):
             dout = gp.to(torch.bfloat16).double()   # the kernel rounds the gathered sum
             extra = U * gp.abs()
         else:
-            dout = _nchw(u["dout"])
+            dout = _nchw(u.dout)
         g = dout * (pre > 0)
         # mask elements whose pre-activation sits at the threshold within rounding
         skip = pre.abs() <= 1e-5 * ((y.abs() + m.abs()) * (rs * gam).abs() + bet.abs()) + TINY
         assert skip.sum().item() <= max(4, 1e-4 * skip.numel()), f"{tag}: threshold band"
     else:
-        g = _nchw(u["dout"])
+        g = _nchw(u.dout)
     sg = g.sum((0, 2, 3))
     sgx = (g * xh).sum((0, 2, 3))
     s1 = g.abs().sum((0, 2, 3))
@@ -165,10 +165,10 @@ def _bn_bwd_checks(rep, tag, u, plan, grads):
              + 1e-6 * a.abs() * (sgx.abs().view(1, -1, 1, 1) / M) * rs * (y.abs() + m.abs()))
     if not isinstance(extra, float):
         bound = bound + a.abs() * extra
-    rep.check(f"bn-bwd {tag}", _nchw(u["dconv"]), ref, bound, skip=skip)
+    rep.check(f"bn-bwd {tag}", _nchw(u.dconv), ref, bound, skip=skip)
     band = 0.0
     if skip is not None:
-        band = ((_nchw(u["dout"]) if kind == "relu" else dout).abs() * (1 + xh.abs())
+        band = ((_nchw(u.dout) if kind == "relu" else dout).abs() * (1 + xh.abs())
                 * skip).sum((0, 2, 3))
     gw, gb = grads[id(bn.weight)], grads[id(bn.bias)]
     rep.check(f"bn-dgamma {tag}", gw, sgx, ACC * s2 + band + TINY)
@@ -199,18 +199,18 @@ def test_every_trunk_launch_bf16(dev, arch, B):
 
     # ---- stem: pair-conv forward, statistics, BN + ReLU inside the max pool
     su = plan.stem_pool["u"]
-    assert su["pair"] and plan.stem_pool["fused"], "bf16 stem: pixel pairs, pool-fused BN"
-    conv = su["conv"]
+    assert su.pair and plan.stem_pool["fused"], "bf16 stem: pixel pairs, pool-fused BN"
+    conv = su.conv
     xb = x.to(torch.bfloat16).double()
     wb = conv.weight.detach().to(torch.bfloat16).double()
-    ref = _conv_refs(xb, wb, _nchw(su["dconv"]), conv.stride, conv.padding)
-    rep.check("fwd stem", _nchw(su["y"]), ref["y"], U * ref["y"].abs() + ACC * ref["y_acc"])
+    ref = _conv_refs(xb, wb, _nchw(su.dconv), conv.stride, conv.padding)
+    rep.check("fwd stem", _nchw(su.y), ref["y"], U * ref["y"].abs() + ACC * ref["y_acc"])
     _bn_fwd_checks(rep, "stem", su, ref)
     n0, h0, w0, c0, p0, q0 = plan.stem_pool["geom"]
-    bn = su["bn"]
-    sc = (bn.weight.detach().double() * su["rstd"].double()).view(1, -1, 1, 1)
-    sh = bn.bias.detach().double().view(1, -1, 1, 1) - su["mean"].double().view(1, -1, 1, 1) * sc
-    ys = _nchw(su["y"])
+    bn = su.bn
+    sc = (bn.weight.detach().double() * su.rstd.double()).view(1, -1, 1, 1)
+    sh = bn.bias.detach().double().view(1, -1, 1, 1) - su.mean.double().view(1, -1, 1, 1) * sc
+    ys = _nchw(su.y)
     t = (ys * sc + sh).clamp(min=0)
     tmag = tF.max_pool2d(ys.abs() * sc.abs() + sh.abs(), 3, 2, 1)  # fp32 y*scale + shift
     pooled = tF.max_pool2d(t, 3, 2, 1)
@@ -226,7 +226,7 @@ def test_every_trunk_launch_bf16(dev, arch, B):
     del ref, t, win
 
     # ---- head of the backward: avgpool
-    xl = plan.blocks[-1][0][-1]["out"]
+    xl = plan.blocks[-1][0][-1].out
     fr = _nchw(xl).mean((2, 3))
     rep.check("avgpool-fwd", plan.feats.double(), fr, U * fr.abs() + 1e-6 * _nchw(xl).abs().mean((2, 3)))
     hw = xl.shape[1] * xl.shape[2]
@@ -238,30 +238,30 @@ def test_every_trunk_launch_bf16(dev, arch, B):
     n_units = 1
     for bi, (bu, ds_u, _shape) in enumerate(plan.blocks):
         tagb = f"b{bi}"
-        assert bu[-1].get("rmask") is not None, "bf16 residual units keep 1-bit masks"
+        assert bu[-1].rmask is not None, "bf16 residual units keep 1-bit masks"
         refs = []
         for k, u in enumerate(bu + ([ds_u] if ds_u is not None else [])):
             n_units += 1
-            conv = u["conv"]
+            conv = u.conv
             tag = f"{tagb}.{'ds' if u is ds_u else k} {tuple(conv.weight.shape)} s{conv.stride}"
-            xin = _nchw(u["x"])
+            xin = _nchw(u.x)
             wb = conv.weight.detach().to(torch.bfloat16).double()
-            ref = _conv_refs(xin, wb, _nchw(u["dconv"]), conv.stride, conv.padding)
-            rep.check(f"fwd {tag}", _nchw(u["y"]), ref["y"],
+            ref = _conv_refs(xin, wb, _nchw(u.dconv), conv.stride, conv.padding)
+            rep.check(f"fwd {tag}", _nchw(u.y), ref["y"],
                       U * ref["y"].abs() + ACC * ref["y_acc"])
             _bn_fwd_checks(rep, tag, u, ref)
             _bn_bwd_checks(rep, tag, u, plan, grads)
             rep.check(f"wgrad {tag}", grads[id(conv.weight)], ref["dw"],
                       ACC * ref["dw_acc"] + TINY)
             if u is not ds_u and k > 0:
-                rep.check(f"dgrad {tag}", _nchw(u["dx"]), ref["dx"],
+                rep.check(f"dgrad {tag}", _nchw(u.dx), ref["dx"],
                           U * ref["dx"].abs() + ACC * ref["dx_acc"])
             refs.append(ref)
             del ref["y"], ref["y_acc"], ref["dw"], ref["dw_acc"]
         # block-input gradient: conv1's dgrad + the downsample's dgrad (two roundings), or
         # + the identity path's masked gradient (accmask: one rounding)
         r1 = refs[0]
-        got = _nchw(bu[0]["dx"])
+        got = _nchw(bu[0].dx)
         if ds_u is not None:
             rd = refs[-1]
             want = r1["dx"] + rd["dx"]
@@ -270,12 +270,12 @@ def test_every_trunk_launch_bf16(dev, arch, B):
             kind = "dgrad-ds"
         else:
             last = bu[-1]
-            mk = _bits(last["rmask"], tuple(last["out"].shape))
-            idn = _nchw(last["dout"]) * mk
+            mk = _bits(last.rmask, tuple(last.out.shape))
+            idn = _nchw(last.dout) * mk
             want = r1["dx"] + idn
             bound = U * want.abs() + ACC * r1["dx_acc"]
             kind = "dgrad-accmask"
-        rep.check(f"{kind} {tagb} s{bu[0]['conv'].stride if ds_u is None else ds_u['conv'].stride}",
+        rep.check(f"{kind} {tagb} s{bu[0].conv.stride if ds_u is None else ds_u.conv.stride}",
                   got, want, bound + TINY)
         del refs
     n_conv = sum(1 for m in trunk.modules() if isinstance(m, mmdx.resnet.Conv2d))
