@@ -727,6 +727,32 @@ int mmdx_amp_update_scale(float* scale, int* growth_tracker, const float* found_
                           void* stream);
 int mmdx_mul_dev_scalar(const float* x, long n, const float* s, float* out, void* stream);
 
+/* ---------------------------------------------------------------- validation metrics
+ * Integer sufficient statistics of the multi-label validation metrics, computed from the
+ * fp32 [N][C] row-major logits / multi-hot targets as the model and the loader produce them
+ * (no transpose, no sort, no workspace).  A target is positive iff target > 0.5.  Every output
+ * is an int64 count accumulated with integer atomics, so the results do not depend on the
+ * order of accumulation: bit-reproducible run to run and exactly comparable with a CPU
+ * reference.  Limits (argument errors): 1 <= C <= 64 and N*C <= 2^24.
+ *
+ * mmdx_auroc_pairs: out int64 [(C+1)][4], zeroed by the entry point.  Row c < C is
+ * {u2, n_pos, n_neg, n_nan} of class c with
+ *   u2 = sum over (i positive, j negative) of 2*[s_i > s_j] + [s_i == s_j]   (IEEE compares:
+ *   -0 == +0 ties, +-inf order like any value; an item with a NaN score adds 0 and is counted
+ *   in n_nan only, so n_pos + n_neg + n_nan = N);
+ * row C is the same statistic over all N*C (score, target) pairs as one class (micro).
+ * AUROC = u2 / (2 n_pos n_neg): Mann-Whitney U with midranks for ties.  Tiled all-pairs
+ * counting: O(N^2 C) compares per-class plus O((N C)^2) micro, which the N*C limit bounds
+ * (u2 <= 2 * 2^48).
+ *
+ * mmdx_confusion_grid: thr fp32 [T], non-decreasing, in LOGIT space, 1 <= T <= 256; tp / fp
+ * int64 [C][T], zeroed by the entry point: tp[c][t] = #{i : target_ic positive and
+ * logit_ic >= thr[t]}, fp[c][t] the same over the negatives (a NaN logit counts nowhere). */
+int mmdx_auroc_pairs(const float* scores, const float* target, int N, int C, int64_t* out,
+                     void* stream);
+int mmdx_confusion_grid(const float* logits, const float* target, int N, int C,
+                        const float* thr, int T, int64_t* tp, int64_t* fp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

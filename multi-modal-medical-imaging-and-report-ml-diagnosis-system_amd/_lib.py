@@ -208,6 +208,8 @@ SIGNATURES = {
     "mmdx_adamw_multi_amp": (i32, [i32, vp, f32, f32, f32, vp, vp, vp, vp]),
     "mmdx_amp_update_scale": (i32, [vp, vp, vp, f32, f32, i32, vp]),
     "mmdx_mul_dev_scalar": (i32, [vp, i64, vp, vp, vp]),
+    "mmdx_auroc_pairs": (i32, [vp, vp, i32, i32, vp, vp]),
+    "mmdx_confusion_grid": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
 }
 
 _lib = None

@@ -16,7 +16,7 @@ from ._lib import call, ptr, stream
 
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
-    "masked_mean", "embed_mean",
+    "masked_mean", "embed_mean", "auroc_counts", "confusion_grid",
 ]
 
 
@@ -406,3 +406,44 @@ class _EmbedMeanFn(torch.autograd.Function):
 
 def embed_mean(ids, mask, table, dt):
     return _EmbedMeanFn.apply(ids.contiguous(), mask.contiguous(), table, dt)
+
+
+# ----------------------------------------------------------------------------- metrics
+def _metric_inputs(name, scores, target):
+    L.require_device(scores, target)
+    if scores.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"{name} takes fp32 scores and targets")
+    if scores.dim() != 2 or scores.shape != target.shape:
+        raise ValueError(f"{name} takes scores and targets of one shape [N, C], got "
+                         f"{tuple(scores.shape)} and {tuple(target.shape)}")
+    return scores.shape
+
+
+def auroc_counts(scores, target):
+    """Pair counts of the AUROC of every class and of the flattened (micro) problem, from
+    fp32 contiguous [N, C] scores and multi-hot targets (positive iff > 0.5): int64
+    [(C + 1), 4] on the device, row c = (u2, n_pos, n_neg, n_nan), row C = micro
+    (mmdx_auroc_pairs; mmdx.metrics.auroc_from_counts turns it into AUROC values on the host).
+    Exact and bit-reproducible; all-pairs counting, so N * C <= 2^24 (and C <= 64).  The
+    inputs are taken as they are: a non-contiguous tensor is an error, not a hidden copy."""
+    N, C = _metric_inputs("auroc_counts", scores, target)
+    out = torch.empty((C + 1, 4), dtype=torch.int64, device=scores.device)
+    call("mmdx_auroc_pairs", ptr(scores), ptr(target), N, C, ptr(out), stream())
+    return out
+
+
+def confusion_grid(logits, target, thr):
+    """(tp, fp), int64 [C, T] on the device: the positives / negatives of every class whose
+    logit is >= thr[t], for a non-decreasing fp32 device vector thr [T] of LOGIT-space
+    thresholds, 1 <= T <= 256 (mmdx_confusion_grid).  Sortedness is the caller's contract: it
+    is not checked (that would be a device-to-host sync)."""
+    N, C = _metric_inputs("confusion_grid", logits, target)
+    L.require_device(thr)
+    if thr.dtype != torch.float32 or thr.dim() != 1:
+        raise TypeError("confusion_grid takes a 1-D fp32 threshold vector")
+    T = thr.numel()
+    tp = torch.empty((C, T), dtype=torch.int64, device=logits.device)
+    fp = torch.empty((C, T), dtype=torch.int64, device=logits.device)
+    call("mmdx_confusion_grid", ptr(logits), ptr(target), N, C, ptr(thr), T, ptr(tp), ptr(fp),
+         stream())
+    return tp, fp

@@ -19,6 +19,10 @@ reference's phases in the reference's order on an MI355X:
 6. generation demo (TP:1066-1099): beam search + disease predictions;
 7. save (TP:1103-1127) into the local registry + local model_bundle.pt.
 
+`val_rows > 0` (not in the reference, whose registry metrics are placeholders, TP:1112) holds
+that many rows out, runs mmdx.metrics.evaluate() on them after the fusion phase and registers
+the measured metrics and the F1-calibrated thresholds instead of the placeholders.
+
 The arguments (all optional) only shrink the run for tests; the defaults are the reference's.
 Report texts need a T5 tokenizer, which cannot be fetched offline: a deterministic
 word-hash stand-in maps them to ids in the t5-small vocabulary (eos 1, pad 0) unless
@@ -148,9 +152,17 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
-                   model_name="fusion_model_T5", device=None, verbose=True):
+                   model_name="fusion_model_T5", device=None, verbose=True, val_rows=0):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
-    prints: tensor shapes, per-step losses and the generated ids / disease vectors."""
+    prints: tensor shapes, per-step losses and the generated ids / disease vectors.
+
+    val_rows = 0 (default) is the reference's run, placeholder registry metrics (TP:1112) and
+    0.5 thresholds included.  val_rows > 0 holds out that many rows (fixed random_state;
+    disjoint from the fusion rows when the frame is large enough, else the overlap is logged
+    - the image tower's warm-up batches draw from the whole frame either way), evaluates on
+    them after the fusion phase (mmdx.metrics.evaluate, with report generation under the run's
+    gen_kwargs), returns that dict as out["val"], and registers its val_auroc_micro / _macro,
+    val_loss, val_f1_micro and val_rougeL (nan stored as None) with the chosen thresholds."""
     from PIL import Image
     from . import training_pipeline as TP
     from .data import LocalCXRBatches
@@ -233,7 +245,19 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             out["text_z_shape"] = tuple(o["embeddings"].shape)
 
     log("----------FUSION MODEL----------")
-    rows = df.sample(n=min(b_fusion, len(df)), random_state=42).reset_index(drop=True)
+    rows = df.sample(n=min(b_fusion, len(df)), random_state=42)
+    val_df = None
+    if val_rows > 0:
+        rest = df.drop(rows.index)
+        if len(rest) >= val_rows:
+            val_df = rest.sample(n=val_rows, random_state=43)
+            log(f"validation: {val_rows} held-out rows, disjoint from the fusion rows")
+        else:
+            val_df = df.sample(n=min(val_rows, len(df)), random_state=43)
+            log(f"validation: {len(val_df)} rows of a {len(df)}-row frame, "
+                f"{len(val_df.index.intersection(rows.index))} of them also fusion rows")
+        val_df = val_df.reset_index(drop=True)
+    rows = rows.reset_index(drop=True)
     from .preprocess import preprocess_batch
     imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev)
     y_multi = torch.tensor(np.stack([np.asarray(v, dtype=np.float32)
@@ -305,13 +329,36 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         log(f"Example report #{i}: {s[:120]}")
         log("Disease vector:", d_preds[i].tolist())
 
+    metrics = {"val_auroc_micro": 0.874, "val_rougeL": 0.214}  # TP:1112 placeholders
+    thresholds = [0.5] * 13
+    if val_df is not None:
+        from .metrics import evaluate
+        log("----------VALIDATION----------")
+        val_rep = t5_tok(val_df["report"].astype(str).tolist(), max_length=256,
+                         truncation=True, padding="max_length", return_tensors="pt")
+        val_labels = val_rep["input_ids"].clone()
+        val_labels[val_rep["attention_mask"] == 0] = -100
+        val = evaluate(image_encoder, text_encoder, fusion_model,
+                       LocalCXRBatches(val_df, _image_root_for(val_df), batch_size=batch_size,
+                                       shuffle=False, device=dev),
+                       generate=True, gen_kwargs=gen, report_labels=val_labels)
+        out["val"] = val
+        metrics = {k: (None if v != v else v) for k, v in
+                   ((k, val[k]) for k in ("val_auroc_micro", "val_auroc_macro", "val_loss",
+                                          "val_f1_micro", "val_rougeL"))}
+        thresholds = val["thresholds"]
+        log(f"[VAL] n={val['n']} loss={val['val_loss']:.4f} auroc micro="
+            f"{val['val_auroc_micro']:.4f} macro={val['val_auroc_macro']:.4f} f1 micro="
+            f"{val['val_f1_micro']:.4f} (at 0.5: {val['val_f1_micro_at_0p5']:.4f}) rougeL="
+            f"{val['val_rougeL']:.4f}")
+
     if save:
         rm = save_model_to_hopsworks_model_registry(
             fusion_model=fusion_model, text_encoder=text_encoder, image_encoder=image_encoder,
             model_name=model_name, description="CXR fusion: CNN+Text -> MLP; multi-label "
                                                "disease head; T5 report head.",
-            metrics={"val_auroc_micro": 0.874, "val_rougeL": 0.214},  # TP:1112 placeholders
-            artifacts={"class_names": list(DISEASES), "thresholds": [0.5] * 13},
+            metrics=metrics,
+            artifacts={"class_names": list(DISEASES), "thresholds": thresholds},
             t5_tokenizer=t5_tok, save_t5_weights=False, hf_model_name="t5-small")
         log("model version in registry:", rm.version)
         out["registry_version"] = rm.version
