@@ -753,6 +753,26 @@ int mmdx_auroc_pairs(const float* scores, const float* target, int N, int C, int
 int mmdx_confusion_grid(const float* logits, const float* target, int N, int C,
                         const float* thr, int T, int64_t* tp, int64_t* fp, void* stream);
 
+/* ---------------------------------------------------------------- Grad-CAM
+ * Heatmaps of the disease head at the trunk's last conv stage.  Between that feature map and
+ * the logits there is only the global average pool and the heads, so the Grad-CAM channel
+ * weights are alpha[b][c][k] = (d logit_c / d pooled_k) / (H W); these two kernels do the rest.
+ * Both are bit-reproducible (fixed summation order, no atomics) and need no workspace.
+ *
+ * mmdx_cam_fwd: raw[b][c][p] = max(0, sum_k alpha[b][c][k] * fmap[b][p][k]), accumulated in
+ * fp32.  fmap [B][HW][K] in `dtype` (the trunk's NHWC activation), alpha fp32 [B][C][K], raw
+ * fp32 [B][C][HW].  K % 8 == 0, C <= 64, HW <= 1024; fmap and alpha 16-byte aligned.
+ *
+ * mmdx_cam_resize: out fp32 [BC][Ho][Wo] = bilinear resize of raw fp32 [BC][H][W] with
+ * half-pixel centres (torch's interpolate(mode="bilinear", align_corners=False): source
+ * coordinate (d + 0.5) * in / out - 0.5 clamped at 0, edges replicated).  normalize != 0 first
+ * divides every map by its own maximum; a maximum <= 0 gives an all-zero map, never NaN.
+ * H * W <= 1024, Ho and Wo <= 4096; out 16-byte aligned. */
+int mmdx_cam_fwd(int dtype, const void* fmap, const float* alpha, int B, int HW, int K, int C,
+                 float* raw, void* stream);
+int mmdx_cam_resize(const float* raw, int BC, int H, int W, int Ho, int Wo, int normalize,
+                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

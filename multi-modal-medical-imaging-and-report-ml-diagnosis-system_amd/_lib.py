@@ -210,6 +210,8 @@ SIGNATURES = {
     "mmdx_mul_dev_scalar": (i32, [vp, i64, vp, vp, vp]),
     "mmdx_auroc_pairs": (i32, [vp, vp, i32, i32, vp, vp]),
     "mmdx_confusion_grid": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "mmdx_cam_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 _lib = None

@@ -16,7 +16,7 @@ from ._lib import call, ptr, stream
 
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
-    "masked_mean", "embed_mean", "auroc_counts", "confusion_grid",
+    "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
 ]
 
 
@@ -447,3 +447,42 @@ def confusion_grid(logits, target, thr):
     call("mmdx_confusion_grid", ptr(logits), ptr(target), N, C, ptr(thr), T, ptr(tp), ptr(fp),
          stream())
     return tp, fp
+
+
+# ----------------------------------------------------------------------------- Grad-CAM
+def cam_raw(fmap, alpha):
+    """raw[b, c, h, w] = relu(sum_k alpha[b, c, k] * fmap[b, h, w, k]), fp32 [B, C, H, W], from
+    the NHWC feature map fmap [B, H, W, K] (fp32, bf16 or fp16) and the fp32 channel weights
+    alpha [B, C, K] (mmdx_cam_fwd: fp32 accumulation, bit-reproducible).  K % 8 == 0, C <= 64,
+    H * W <= 1024.  The inputs are taken as they are: a non-contiguous tensor is an error."""
+    L.require_device(fmap, alpha)
+    if alpha.dtype != torch.float32:
+        raise TypeError("cam_raw takes fp32 channel weights (alpha)")
+    dt = L.dtype_code(fmap.dtype)
+    if fmap.dim() != 4 or alpha.dim() != 3 or alpha.shape[0] != fmap.shape[0] or \
+            alpha.shape[2] != fmap.shape[3]:
+        raise ValueError(f"cam_raw takes fmap [B, H, W, K] and alpha [B, C, K], got "
+                         f"{tuple(fmap.shape)} and {tuple(alpha.shape)}")
+    B, H, W, K = fmap.shape
+    C = alpha.shape[1]
+    raw = torch.empty((B, C, H, W), dtype=torch.float32, device=fmap.device)
+    call("mmdx_cam_fwd", dt, ptr(fmap), ptr(alpha), B, H * W, K, C, ptr(raw), stream())
+    return raw
+
+
+def cam_resize(raw, out_size, normalize=True):
+    """Bilinear resize (half-pixel centres, as torch's interpolate with align_corners=False) of
+    the fp32 maps raw [..., H, W] to [..., Ho, Wo]; normalize=True first divides every map by
+    its own maximum, an all-zero map staying all zero (mmdx_cam_resize).  H * W <= 1024,
+    Ho, Wo <= 4096."""
+    L.require_device(raw)
+    if raw.dtype != torch.float32:
+        raise TypeError("cam_resize takes fp32 maps")
+    if raw.dim() < 2:
+        raise ValueError(f"cam_resize takes maps [..., H, W], got {tuple(raw.shape)}")
+    Ho, Wo = (int(v) for v in out_size)
+    H, W = raw.shape[-2:]
+    out = torch.empty((*raw.shape[:-2], Ho, Wo), dtype=torch.float32, device=raw.device)
+    call("mmdx_cam_resize", ptr(raw), raw.numel() // (H * W) if H * W else 0, H, W, Ho, Wo,
+         int(bool(normalize)), ptr(out), stream())
+    return out

@@ -217,6 +217,18 @@ class ResNetTrunk(nn.Sequential):
         feats = _TrunkFn.apply(x.contiguous(), self, need_grad, *params)
         return feats.view(feats.shape[0], feats.shape[1], 1, 1)
 
+    @torch.no_grad()
+    def forward_features(self, x):
+        """(feats [B, K], fmap [B, H, W, K]) in the compute dtype: the pooled features `forward`
+        returns and the layer4 activation they are the spatial mean of (NHWC), for Grad-CAM
+        (explain.py).  Inference only: eval mode, no autograd graph; the same plan and plan
+        cache entry as an eval-mode `forward` under no_grad, both outputs cloned out of its
+        arena."""
+        if self.training:
+            raise RuntimeError("forward_features is an eval-mode call: trunk.eval() first")
+        plan = _run_fwd_plan(x.contiguous(), self, False, self.engine_params())
+        return plan.feats.clone(), plan.top.clone()
+
 
 # ----------------------------------------------------------------------------- engine
 # The trunk is executed from launch plans (plan.py; include/mmdx.h, csrc/plan.cpp): the
@@ -766,6 +778,7 @@ class _Plan:
             r.pack_at_head()
         H, W, C = hwc
         self.feats = r.buf((N, C))
+        self.top = x  # layer4's output [N, H, W, C] (forward_features; Grad-CAM reads it)
         r.fw.add(L.OP_AVGPOOL_FWD, r.dt, i=(N, H * W, C), p=(x, self.feats))
         self.out_geom = (N, H, W, C)
         self.bwd = None
@@ -871,34 +884,41 @@ def _plans_for(trunk, key, build):
     return plan_cache_get(cache, key, build)
 
 
+def _run_fwd_plan(x, trunk, keep, params):
+    """Replay the forward plan of (x's shape, the trunk's dtype and mode, keep, params),
+    recording it first if need be; returns the plan, whose arena then holds the activations."""
+    L.require_device(x)
+    T = trunk.compute_dtype
+    train = trunk.training
+    dev = x.device
+    if x.dim() != 4:
+        raise ValueError("expected images [B,3,H,W]")
+    if x.dtype == torch.float32 and x.shape[1] == 3:
+        N, cin, H, W = x.shape
+        in_nchw = True
+    else:  # pre-converted NHWC, channel-padded
+        N, H, W, cin = x.shape
+        in_nchw = False
+        if x.dtype != T:
+            raise TypeError("NHWC trunk input must already be in the compute dtype")
+    key = (N, H, W, cin, in_nchw, T, train, keep, dev.index,
+           tuple(p.data_ptr() for p in params), L.lib().mmdx_bn_bwd_pair_enabled())
+    plan = _plans_for(trunk, key,
+                      lambda: _Plan(trunk, N, H, W, in_nchw, cin, T, train, keep, dev))
+    # the downsample branches run on the side stream (joined inside the plan)
+    plan.fwd.run([x.data_ptr()], [stream(), _side_stream(trunk, dev).cuda_stream],
+                 timer=CONV_TIMER)
+    if train:  # every BN's num_batches_tracked += 1, in one multi-tensor launch
+        torch._foreach_add_([m.num_batches_tracked for m in trunk.modules()
+                             if isinstance(m, BatchNorm2d)], 1)
+    return plan
+
+
 class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, trunk, need_grad, *params):
-        L.require_device(x)
-        T = trunk.compute_dtype
-        train = trunk.training
         keep = bool(need_grad)
-        dev = x.device
-        if x.dim() != 4:
-            raise ValueError("expected images [B,3,H,W]")
-        if x.dtype == torch.float32 and x.shape[1] == 3:
-            N, cin, H, W = x.shape
-            in_nchw = True
-        else:  # pre-converted NHWC, channel-padded
-            N, H, W, cin = x.shape
-            in_nchw = False
-            if x.dtype != T:
-                raise TypeError("NHWC trunk input must already be in the compute dtype")
-        key = (N, H, W, cin, in_nchw, T, train, keep, dev.index,
-               tuple(p.data_ptr() for p in params), L.lib().mmdx_bn_bwd_pair_enabled())
-        plan = _plans_for(trunk, key,
-                          lambda: _Plan(trunk, N, H, W, in_nchw, cin, T, train, keep, dev))
-        # the downsample branches run on the side stream (joined inside the plan)
-        plan.fwd.run([x.data_ptr()], [stream(), _side_stream(trunk, dev).cuda_stream],
-                     timer=CONV_TIMER)
-        if train:  # every BN's num_batches_tracked += 1, in one multi-tensor launch
-            torch._foreach_add_([m.num_batches_tracked for m in trunk.modules()
-                                 if isinstance(m, BatchNorm2d)], 1)
+        plan = _run_fwd_plan(x, trunk, keep, params)
         if keep:
             tok = _Token()
             plan.arena.owner = weakref.ref(tok)
