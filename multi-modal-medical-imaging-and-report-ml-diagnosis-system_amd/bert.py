@@ -5,8 +5,11 @@ The reference builds it with `AutoModel.from_pretrained("bert-base-uncased")`
 BertEmbeddings / BertLayer (modeling_bert.py).  Here each BertLayer is ONE autograd node:
 fused QKV GEMM -> attention core (MFMA, in-LDS softmax) -> out-proj GEMM -> Add&LayerNorm ->
 FFN up GEMM (+GELU epilogue) -> FFN down GEMM -> Add&LayerNorm, with a hand-sequenced
-backward whose residual gradients are summed inside GEMM epilogues (beta = 1).
-Hidden-state dropout runs on the mmdx dropout kernel in train mode; attention-probability
+backward whose residual gradients are summed inside GEMM epilogues (beta = 1).  The layer
+is written once, in xlayers (bert_fwd / bert_bwd): _BertLayerFn here issues it call by call
+(inference, no_grad, a frozen encoder parameter), xplan records the same body as a launch
+plan for the whole stack (training).
+Hidden-state dropout runs inside the LayerNorm kernel in train mode; attention-probability
 dropout (BertSelfAttention's, p = config.attention_probs_dropout_prob) is fused into the
 attention kernel (counter-based hash, keep bit carried in the saved probabilities' sign).
 RNG streams cannot match torch's, so parity runs use p = 0 on both sides; the dropout
@@ -14,7 +17,6 @@ arithmetic itself is checked against an explicit masked reference (tests/test_te
 """
 from __future__ import annotations
 
-import math
 from types import SimpleNamespace
 
 import torch
@@ -22,6 +24,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import functional as F
+from . import xlayers as XL
+from . import xplan
 from ._lib import call, ptr, stream
 from .layers import Embedding, LayerNorm, Linear
 
@@ -30,205 +34,33 @@ class _Out(SimpleNamespace):
     pass
 
 
-def _cat_cast(ws, T, device):
-    """Concatenate fp32 tensors along dim 0 into one compute-dtype buffer (device casts)."""
-    rows = sum(w.shape[0] for w in ws)
-    out = torch.empty((rows,) + tuple(ws[0].shape[1:]), dtype=T, device=device)
-    o = 0
-    for w in ws:
-        n = w.shape[0]
-        call("mmdx_cast", L.dtype_code(T), L.F32, ptr(w), w.numel(), ptr(out[o:o + n]), stream())
-        o += n
-    return out
-
-
-def _ws(n, dev):
-    return L.workspace(n, dev)
-
-
-def _ln_bwd(xs, dy, gamma, mean, rstd):
-    D = xs.shape[-1]
-    rows = xs.numel() // D
-    dx = torch.empty_like(xs)
-    dg = torch.empty(D, dtype=torch.float32, device=xs.device)
-    db = torch.empty(D, dtype=torch.float32, device=xs.device)
-    n = L.lib().mmdx_layernorm_workspace_size(rows, D)
-    w = _ws(n, xs.device)
-    call("mmdx_layernorm_bwd", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D, ptr(gamma),
-         ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db), 0.0, ptr(w), n, stream())
-    return dx, dg, db
-
-
-def _ln_fwd(x, res, gamma, beta, eps):
-    D = x.shape[-1]
-    rows = x.numel() // D
-    y = torch.empty_like(x)
-    xs = torch.empty_like(x)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    call("mmdx_layernorm_fwd", L.dtype_code(x.dtype), ptr(x), ptr(res), rows, D, ptr(gamma),
-         ptr(beta), float(eps), ptr(y), ptr(xs), ptr(mean), ptr(rstd), stream())
-    return y, xs, mean, rstd
-
-
-def _ln_fwd_drop(x, res, gamma, beta, eps, p, seed):
-    """LayerNorm(dropout(x) + res) in one pass; returns (y, xsum, mean, rstd, rng)."""
-    D = x.shape[-1]
-    rows = x.numel() // D
-    y = torch.empty_like(x)
-    xs = torch.empty_like(x)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rng = torch.empty(1, dtype=torch.int64, device=x.device)
-    call("mmdx_layernorm_fwd_dropout", L.dtype_code(x.dtype), ptr(x), ptr(res), rows, D,
-         ptr(gamma), ptr(beta), float(eps), float(p), L.dropout_seed(seed),
-         ptr(L.rng_counter(x.device)), ptr(y), ptr(xs), ptr(mean), ptr(rstd), ptr(rng), stream())
-    return y, xs, mean, rstd, rng
-
-
-def _ln_bwd_drop(xs, dy, gamma, mean, rstd, p, rng):
-    """(d xsum, its dropout backward, dgamma, dbeta)."""
-    D = xs.shape[-1]
-    rows = xs.numel() // D
-    dx = torch.empty_like(xs)
-    dxd = torch.empty_like(xs)
-    dg = torch.empty(D, dtype=torch.float32, device=xs.device)
-    db = torch.empty(D, dtype=torch.float32, device=xs.device)
-    n = L.lib().mmdx_layernorm_workspace_size(rows, D)
-    w = _ws(n, xs.device)
-    call("mmdx_layernorm_bwd_dropout", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D,
-         ptr(gamma), ptr(mean), ptr(rstd), float(p), ptr(rng), ptr(dx), ptr(dxd), ptr(dg),
-         ptr(db), 0.0, ptr(w), n, stream())
-    return dx, dxd, dg, db
-
-
-def _dropout_fwd(x, p, seed):
-    y = torch.empty_like(x)
-    m = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    call("mmdx_dropout_fwd", L.dtype_code(x.dtype), ptr(x), x.numel(), float(p),
-         L.dropout_seed(seed), 0, ptr(L.rng_counter(x.device)), ptr(y), ptr(m), stream())
-    return y, m
-
-
-def _dropout_bwd(dy, m, p):
-    dx = torch.empty_like(dy)
-    call("mmdx_dropout_bwd", L.dtype_code(dy.dtype), ptr(dy), ptr(m), dy.numel(), float(p),
-         ptr(dx), stream())
-    return dx
-
-
-_SEED = [0xB127]
-
-
 class _BertLayerFn(torch.autograd.Function):
-    """One transformers BertLayer (post-LN) forward/backward on mmdx kernels."""
+    """One transformers BertLayer (post-LN): xlayers.bert_fwd / bert_bwd issued at once."""
 
     @staticmethod
-    def forward(ctx, h, mask, cfg, wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2,
-                b2):
+    def forward(ctx, h, mask, cfg, *params):
         B, Ls, D = h.shape
-        Hn, eps, p = cfg.num_attention_heads, cfg.layer_norm_eps, cfg.p_hidden
-        T = h.dtype
-        dev = h.device
-        M = B * Ls
-        x = h.reshape(M, D)
-        wqkv = _cat_cast([wq, wk, wv], T, dev)
-        bqkv = torch.empty(3 * D, dtype=torch.float32, device=dev)
-        for i, bb in enumerate((bq, bk, bv)):
-            call("mmdx_axpby", D, 1.0, ptr(bb), 0.0, None, ptr(bqkv[i * D:(i + 1) * D]),
-                 stream())
-        qkv = torch.empty((M, 3 * D), dtype=T, device=dev)
-        F.gemm(x, D, True, wqkv, D, True, M, 3 * D, D, qkv, 3 * D, bias=bqkv, compute_dtype=T)
-        att = torch.empty((M, D), dtype=T, device=dev)
         keep = any(ctx.needs_input_grad)
-        scale = 1.0 / math.sqrt(D // Hn)
-        # BertSelfAttention's dropout on attention_probs (train mode), fused in the kernel
-        pa = float(cfg.p_attn) if (cfg.training and keep) else 0.0
-        if pa > 0:
-            _SEED[0] += 1
-        ctx.attn = F.attention_fwd(qkv, mask, B, Ls, Hn, scale, pa,
-                                   L.dropout_seed(_SEED[0]) if pa > 0 else 0,
-                                   L.rng_counter(dev), att, keep)
-        woc = F.cast(wo, T)
-        a = torch.empty((M, D), dtype=T, device=dev)
-        F.gemm(att, D, True, woc, D, True, M, D, D, a, D, bias=bo, compute_dtype=T)
-        m1 = None
-        if p > 0 and cfg.training:   # dropout inside the LayerNorm pass (keep bits in m1)
-            _SEED[0] += 1
-            h1, xs1, mu1, rs1, m1 = _ln_fwd_drop(a, x, g1, b1, eps, p, _SEED[0])
-        else:
-            h1, xs1, mu1, rs1 = _ln_fwd(a, x, g1, b1, eps)
-        wic = F.cast(wi, T)
-        I = wi.shape[0]
-        f = torch.empty((M, I), dtype=T, device=dev)
-        pre = torch.empty((M, I), dtype=T, device=dev)
-        F.gemm(h1, D, True, wic, D, True, M, I, D, f, I, bias=bi, act=L.ACT_GELU, preact=pre,
-               compute_dtype=T)
-        wo2c = F.cast(wo2, T)
-        f2 = torch.empty((M, D), dtype=T, device=dev)
-        F.gemm(f, I, True, wo2c, I, True, M, D, I, f2, D, bias=bo2, compute_dtype=T)
-        m2 = None
-        if p > 0 and cfg.training:
-            _SEED[0] += 1
-            h2, xs2, mu2, rs2, m2 = _ln_fwd_drop(f2, h1, g2, b2, eps, p, _SEED[0])
-        else:
-            h2, xs2, mu2, rs2 = _ln_fwd(f2, h1, g2, b2, eps)
-        ctx.save_for_backward(x, mask, wqkv, qkv, att, woc, xs1, mu1, rs1, g1, h1, wic,
-                              pre, f, wo2c, xs2, mu2, rs2, g2)
-        ctx.m1, ctx.m2, ctx.p, ctx.pa = m1, m2, p, pa
-        ctx.dims = (B, Ls, D, Hn, I, scale)
+        ctx.c = c = SimpleNamespace(
+            B=B, Ls=Ls, D=D, H=cfg.num_attention_heads, I=params[10].shape[0],
+            eps=cfg.layer_norm_eps, p=cfg.p_hidden if cfg.training else 0.0,
+            pa=float(cfg.p_attn) if (cfg.training and keep) else 0.0)
+        be = XL.Eager(h.dtype, h.device, keep)
+        h2, saved = XL.bert_fwd(be, 0, h.reshape(B * Ls, D), mask, params, c)
+        if keep:
+            XL.save(ctx, dict(saved, mask=mask))
         return h2.reshape(B, Ls, D)
 
     @staticmethod
     def backward(ctx, dh2):
-        (x, mask, wqkv, qkv, att, woc, xs1, mu1, rs1, g1, h1, wic, pre, f, wo2c, xs2, mu2,
-         rs2, g2) = ctx.saved_tensors
-        B, Ls, D, Hn, I, scale = ctx.dims
-        T = x.dtype
-        dev = x.device
-        M = B * Ls
-        dh2 = F.cast(dh2.contiguous().reshape(M, D), T)
-        # LN2: X = d(f2 + h1)
-        if ctx.m2 is not None:
-            X, dX2, dg2, db2 = _ln_bwd_drop(xs2, dh2, g2, mu2, rs2, ctx.p, ctx.m2)
-        else:
-            X, dg2, db2 = _ln_bwd(xs2, dh2, g2, mu2, rs2)
-            dX2 = X
-        # FFN down: f2 = f Wo2^T + bo2
-        # dpre = (dX2 Wo2) * gelu'(pre): the GELU backward in the GEMM epilogue
-        dpre = torch.empty((M, I), dtype=T, device=dev)
-        F.gemm(dX2, D, True, wo2c, I, False, M, I, D, dpre, I, act=L.ACT_GELU_BWD, preact=pre,
-               compute_dtype=T)
-        dWo2 = torch.empty((D, I), dtype=torch.float32, device=dev)
-        dbo2 = torch.empty(D, dtype=torch.float32, device=dev)
-        F.gemm_wgrad_bias(dX2, D, f, I, D, I, M, dWo2, I, dbo2, compute_dtype=T)
-        dWi = torch.empty((I, D), dtype=torch.float32, device=dev)
-        dbi = torch.empty(I, dtype=torch.float32, device=dev)
-        F.gemm_wgrad_bias(dpre, I, h1, D, I, D, M, dWi, D, dbi, compute_dtype=T)
-        # X := dpre Wi + X  (residual into h1)
-        F.gemm(dpre, I, True, wic, D, False, M, D, I, X, D, beta=1.0, compute_dtype=T)
-        # LN1: Y = d(a + x)
-        if ctx.m1 is not None:
-            Y, dY1, dg1, db1 = _ln_bwd_drop(xs1, X, g1, mu1, rs1, ctx.p, ctx.m1)
-        else:
-            Y, dg1, db1 = _ln_bwd(xs1, X, g1, mu1, rs1)
-            dY1 = Y
-        datt = torch.empty((M, D), dtype=T, device=dev)
-        F.gemm(dY1, D, True, woc, D, False, M, D, D, datt, D, compute_dtype=T)
-        dWo = torch.empty((D, D), dtype=torch.float32, device=dev)
-        dbo = torch.empty(D, dtype=torch.float32, device=dev)
-        F.gemm_wgrad_bias(dY1, D, att, D, D, D, M, dWo, D, dbo, compute_dtype=T)
-        dqkv = torch.empty((M, 3 * D), dtype=T, device=dev)
-        F.attention_bwd(qkv, ctx.attn, att, datt, mask, B, Ls, Hn, scale, ctx.pa, dqkv)
-        dWqkv = torch.empty((3 * D, D), dtype=torch.float32, device=dev)
-        dbqkv = torch.empty(3 * D, dtype=torch.float32, device=dev)
-        F.gemm_wgrad_bias(dqkv, 3 * D, x, D, 3 * D, D, M, dWqkv, D, dbqkv, compute_dtype=T)
-        # Y := dqkv Wqkv + Y  (residual into x)
-        F.gemm(dqkv, 3 * D, True, wqkv, D, False, M, D, 3 * D, Y, D, beta=1.0, compute_dtype=T)
-        dx = Y.reshape(B, Ls, D)
-        return (dx, None, None,
-                dWqkv[:D], dbqkv[:D], dWqkv[D:2 * D], dbqkv[D:2 * D], dWqkv[2 * D:],
-                dbqkv[2 * D:], dWo, dbo, dg1, db1, dWi, dbi, dWo2, dbo2, dg2, db2)
+        c, s = ctx.c, XL.load(ctx)
+        x = s["x"]
+        be = XL.Eager(x.dtype, x.device, True)
+        table = XL.bert_grads(c.D, c.I)
+        gd = be.grad_bufs(table)
+        dh2 = F.cast(dh2.contiguous().reshape(x.shape), x.dtype)
+        dx = XL.bert_bwd(be, s, dh2, s["mask"], gd, c)
+        return (dx.reshape(c.B, c.Ls, c.D), None, None, *XL.in_param_order(table, gd, 16))
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -254,7 +86,7 @@ class _EmbedFn(torch.autograd.Function):
         B, Ls = ids.shape
         D = xs.shape[-1]
         dy = F.cast(dy.contiguous(), xs.dtype)
-        dx, dg, db = _ln_bwd(xs, dy, gamma, mean, rstd)
+        dx, dg, db = F.ln_bwd(xs, dy, gamma, mean, rstd)
         dev = ids.device
         ws, ps, ts = ctx.shapes
         dword = torch.zeros(ws, dtype=torch.float32, device=dev)
@@ -397,7 +229,6 @@ class BertModel(nn.Module):
                               training=self.training)
         # the whole layer stack as one native launch plan per direction (xplan); the eager
         # per-layer nodes when gradients are off or some encoder parameter is frozen
-        from . import xplan
         params = [q for layer in self.encoder.layer for q in layer.params()]
         keep = torch.is_grad_enabled()
         pcfg = SimpleNamespace(heads=self.config.num_attention_heads,

@@ -111,17 +111,6 @@ DEBUG = {"spin_limit": 0, "flags": 0}
 BWD_COOP = os.environ.get("MMDX_LSTM_BWD_COOP", "0") == "1"
 
 
-def _cat_cast(ws, T, dev):
-    rows = sum(w.shape[0] for w in ws)
-    out = torch.empty((rows,) + tuple(ws[0].shape[1:]), dtype=T, device=dev)
-    o = 0
-    for w in ws:
-        n = w.shape[0]
-        call("mmdx_cast", L.dtype_code(T), L.F32, ptr(w), w.numel(), ptr(out[o:o + n]), stream())
-        o += n
-    return out
-
-
 class _LSTMLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, H, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r):
@@ -130,8 +119,8 @@ class _LSTMLayerFn(torch.autograd.Function):
         dev = x.device
         M = B * Ls
         G4 = 4 * H
-        wih = _cat_cast([wih_f, wih_r], T, dev)                 # [8H, In]
-        whh = _cat_cast([whh_f, whh_r], T, dev)                 # [2*4H, H]
+        wih = F.cat_cast([wih_f, wih_r], T, dev)                 # [8H, In]
+        whh = F.cat_cast([whh_f, whh_r], T, dev)                 # [2*4H, H]
         bias = torch.empty(2 * G4, dtype=torch.float32, device=dev)
         call("mmdx_axpby", G4, 1.0, ptr(bih_f), 1.0, ptr(bhh_f), ptr(bias[:G4]), stream())
         call("mmdx_axpby", G4, 1.0, ptr(bih_r), 1.0, ptr(bhh_r), ptr(bias[G4:]), stream())

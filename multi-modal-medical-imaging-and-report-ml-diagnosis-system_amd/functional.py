@@ -21,17 +21,11 @@ __all__ = [
 
 
 class _NoTimer:
-    def __call__(self, flops):
-        return self
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+    active = False
 
 
-# bench.py installs a HIP-event timer here to measure the dense GEMM launches (C5 roofline).
+# bench.py installs a HIP-event timer here to measure the dense GEMM launches (C5 roofline):
+# while it is `active`, timer(cost) is a context manager around each launch (_timed)
 GEMM_TIMER = _NoTimer()
 
 
@@ -89,6 +83,17 @@ def gemm_cost(M, N, K, dt, c_dt, beta=0.0, act=L.ACT_NONE, preact=None):
     return LaunchCost("gemm", 2 * M * N * K, b, f"{M}x{N}x{K}")
 
 
+def _timed(cost, name, *args):
+    """One dense-GEMM launch, between the timer's events while a timer is active (as the
+    launch plans ask: plan._OpList.run); its cost record (gemm_cost's arguments) is built
+    only then."""
+    if getattr(GEMM_TIMER, "active", False):
+        with GEMM_TIMER(gemm_cost(*cost)):
+            call(name, *args)
+    else:
+        call(name, *args)
+
+
 # ----------------------------------------------------------------------------- primitives
 def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, M, N, K, Cout, ldc, *, bias=None, addend=None,
          act=L.ACT_NONE, alpha=1.0, beta=0.0, preact=None, compute_dtype=None, residual=None):
@@ -97,19 +102,12 @@ def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, M, N, K, Cout, ldc, *, bias=None, a
     dt = L.dtype_code(compute_dtype if compute_dtype is not None else A.dtype)
     ws_n = L.lib().mmdx_gemm_workspace_size(dt, M, N, K)
     ws = L.workspace(ws_n, Cout.device)
-    cost = gemm_cost(M, N, K, dt, L.dtype_code(Cout.dtype),
-                     1.0 if residual is not None else beta, act, preact)
-    with GEMM_TIMER(cost):
-        if residual is not None:
-            call("mmdx_gemm_res", dt, M, N, K, ptr(A), lda, int(a_kmajor), ptr(B), ldb,
-                 int(b_kmajor), ptr(Cout), ldc, L.dtype_code(Cout.dtype), ptr(bias),
-                 ptr(addend), act, float(alpha), float(beta), ptr(preact), ptr(residual),
-                 ptr(ws), ws_n, stream())
-        else:
-            call("mmdx_gemm", dt, M, N, K, ptr(A), lda, int(a_kmajor), ptr(B), ldb,
-                 int(b_kmajor), ptr(Cout), ldc, L.dtype_code(Cout.dtype), ptr(bias),
-                 ptr(addend), act, float(alpha), float(beta), ptr(preact), ptr(ws), ws_n,
-                 stream())
+    c_dt = L.dtype_code(Cout.dtype)
+    res = () if residual is None else (ptr(residual),)
+    _timed((M, N, K, dt, c_dt, 1.0 if residual is not None else beta, act, preact),
+           "mmdx_gemm_res" if res else "mmdx_gemm", dt, M, N, K, ptr(A), lda, int(a_kmajor),
+           ptr(B), ldb, int(b_kmajor), ptr(Cout), ldc, c_dt, ptr(bias), ptr(addend), act,
+           float(alpha), float(beta), ptr(preact), *res, ptr(ws), ws_n, stream())
     return Cout
 
 
@@ -119,9 +117,9 @@ def gemm_wgrad_bias(dY, ldy, X, ldx, M, N, K, dW, ldw, db, *, compute_dtype=None
     dt = L.dtype_code(compute_dtype if compute_dtype is not None else dY.dtype)
     ws_n = L.lib().mmdx_gemm_bias_grad_workspace_size(dt, M, N, K)
     ws = L.workspace(ws_n, dW.device)
-    with GEMM_TIMER(gemm_cost(M, N, K, dt, L.dtype_code(dW.dtype), 0.0, L.ACT_NONE, None)):
-        call("mmdx_gemm_bias_grad", dt, M, N, K, ptr(dY), ldy, ptr(X), ldx, ptr(dW), ldw,
-             L.dtype_code(dW.dtype), ptr(db), ptr(ws), ws_n, stream())
+    c_dt = L.dtype_code(dW.dtype)
+    _timed((M, N, K, dt, c_dt, 0.0, L.ACT_NONE, None), "mmdx_gemm_bias_grad", dt, M, N, K,
+           ptr(dY), ldy, ptr(X), ldx, ptr(dW), ldw, c_dt, ptr(db), ptr(ws), ws_n, stream())
     return dW, db
 
 
@@ -134,6 +132,107 @@ def cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     call("mmdx_cast", L.dtype_code(dtype), L.dtype_code(x.dtype), ptr(x), x.numel(), ptr(y),
          stream())
     return y
+
+
+def cat_cast(ws, T, device):
+    """Concatenate fp32 tensors along dim 0 into one compute-dtype buffer (device casts)."""
+    rows = sum(w.shape[0] for w in ws)
+    out = torch.empty((rows,) + tuple(ws[0].shape[1:]), dtype=T, device=device)
+    o = 0
+    for w in ws:
+        n = w.shape[0]
+        call("mmdx_cast", L.dtype_code(T), L.F32, ptr(w), w.numel(), ptr(out[o:o + n]), stream())
+        o += n
+    return out
+
+
+def add(x, y, out=None):
+    out = torch.empty_like(x) if out is None else out
+    call("mmdx_add", L.dtype_code(x.dtype), x.numel(), ptr(x), ptr(y), ptr(out), stream())
+    return out
+
+
+# Eager one-op wrappers: they allocate what they return; `out=` (the same tuple) writes into
+# the caller's buffers instead.
+def _f32(n, like):
+    return torch.empty(n, dtype=torch.float32, device=like.device)
+
+
+def ln_fwd(x, res, gamma, beta, eps, want_sum=True):
+    """LayerNorm(x (+ res)) over the last dim -> (y, x + res or None, mean, rstd); the sum
+    is what the backward reads (x itself when there is no residual)."""
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty_like(x)
+    xs = torch.empty_like(x) if want_sum else None
+    mean, rstd = _f32(rows, x), _f32(rows, x)
+    call("mmdx_layernorm_fwd", L.dtype_code(x.dtype), ptr(x), ptr(res), rows, D, ptr(gamma),
+         ptr(beta), float(eps), ptr(y), ptr(xs), ptr(mean), ptr(rstd), stream())
+    return y, xs, mean, rstd
+
+
+def ln_fwd_drop(x, res, gamma, beta, eps, p, seed):
+    """LayerNorm(dropout(x) + res) in one pass -> (y, xsum, mean, rstd, rng); rng is the
+    dropout stream base the backward redraws the keep bits from.  seed: L.dropout_seed's."""
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y, xs = torch.empty_like(x), torch.empty_like(x)
+    mean, rstd = _f32(rows, x), _f32(rows, x)
+    rng = torch.empty(1, dtype=torch.int64, device=x.device)
+    call("mmdx_layernorm_fwd_dropout", L.dtype_code(x.dtype), ptr(x), ptr(res), rows, D,
+         ptr(gamma), ptr(beta), float(eps), float(p), seed, ptr(L.rng_counter(x.device)),
+         ptr(y), ptr(xs), ptr(mean), ptr(rstd), ptr(rng), stream())
+    return y, xs, mean, rstd, rng
+
+
+def ln_bwd(xs, dy, gamma, mean, rstd, addin=None, out=None):
+    """LayerNorm backward -> (dx, dgamma, dbeta); addin: a residual branch's gradient added
+    to dx in the same pass (mmdx_layernorm_bwd_residual)."""
+    D = xs.shape[-1]
+    rows = xs.numel() // D
+    dx, dg, db = out or (torch.empty_like(xs), _f32(D, xs), _f32(D, xs))
+    n = L.lib().mmdx_layernorm_workspace_size(rows, D)
+    w = L.workspace(n, xs.device)
+    if addin is not None:
+        call("mmdx_layernorm_bwd_residual", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D,
+             ptr(gamma), ptr(mean), ptr(rstd), ptr(addin), ptr(dx), ptr(dg), ptr(db), 0.0,
+             ptr(w), n, stream())
+    else:
+        call("mmdx_layernorm_bwd", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D,
+             ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db), 0.0, ptr(w), n,
+             stream())
+    return dx, dg, db
+
+
+def ln_bwd_drop(xs, dy, gamma, mean, rstd, p, rng, out=None):
+    """Backward of ln_fwd_drop -> (d xsum, its dropout backward, dgamma, dbeta)."""
+    D = xs.shape[-1]
+    rows = xs.numel() // D
+    dx, dxd, dg, db = out or (torch.empty_like(xs), torch.empty_like(xs), _f32(D, xs),
+                              _f32(D, xs))
+    n = L.lib().mmdx_layernorm_workspace_size(rows, D)
+    w = L.workspace(n, xs.device)
+    call("mmdx_layernorm_bwd_dropout", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D,
+         ptr(gamma), ptr(mean), ptr(rstd), float(p), ptr(rng), ptr(dx), ptr(dxd), ptr(dg),
+         ptr(db), 0.0, ptr(w), n, stream())
+    return dx, dxd, dg, db
+
+
+def dropout_fwd(x, p, seed, offset=0):
+    """-> (dropped x, uint8 keep mask); seed: L.dropout_seed's.  The device counter
+    (L.rng_counter) advances per launch."""
+    y = torch.empty_like(x)
+    mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    call("mmdx_dropout_fwd", L.dtype_code(x.dtype), ptr(x), x.numel(), float(p), seed, offset,
+         ptr(L.rng_counter(x.device)), ptr(y), ptr(mask), stream())
+    return y, mask
+
+
+def dropout_bwd(dy, mask, p):
+    dx = torch.empty_like(dy)
+    call("mmdx_dropout_bwd", L.dtype_code(dy.dtype), ptr(dy), ptr(mask), dy.numel(), float(p),
+         ptr(dx), stream())
+    return dx
 
 
 def _bias_grad(dy, M, N, out):
@@ -254,15 +353,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, eps):
         L.require_device(x, residual, gamma, beta)
-        D = x.shape[-1]
-        rows = x.numel() // D
-        y = torch.empty_like(x)
-        xs = torch.empty_like(x)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        call("mmdx_layernorm_fwd", L.dtype_code(x.dtype), ptr(x), ptr(residual), rows, D,
-             ptr(gamma), ptr(beta), float(eps), ptr(y), ptr(xs), ptr(mean), ptr(rstd),
-             stream())
+        y, xs, mean, rstd = ln_fwd(x, residual, gamma, beta, eps)
         ctx.save_for_backward(xs, gamma, mean, rstd)
         ctx.has_res = residual is not None
         return y
@@ -270,17 +361,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xs, gamma, mean, rstd = ctx.saved_tensors
-        D = xs.shape[-1]
-        rows = xs.numel() // D
-        dy = cast(dy.contiguous(), xs.dtype)
-        dx = torch.empty_like(xs)
-        dg = torch.empty(D, dtype=torch.float32, device=xs.device)
-        db = torch.empty(D, dtype=torch.float32, device=xs.device)
-        ws_n = L.lib().mmdx_layernorm_workspace_size(rows, D)
-        ws = L.workspace(ws_n, xs.device)
-        call("mmdx_layernorm_bwd", L.dtype_code(xs.dtype), ptr(xs), ptr(dy), rows, D,
-             ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db), 0.0, ptr(ws), ws_n,
-             stream())
+        dx, dg, db = ln_bwd(xs, cast(dy.contiguous(), xs.dtype), gamma, mean, rstd)
         return dx, (dx if ctx.has_res else None), dg, db, None
 
 
@@ -295,10 +376,7 @@ _DROPOUT_SEED = [0x5EED]
 class _DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed, offset):
-        y = torch.empty_like(x)
-        mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-        call("mmdx_dropout_fwd", L.dtype_code(x.dtype), ptr(x), x.numel(), float(p), seed,
-             offset, ptr(L.rng_counter(x.device)), ptr(y), ptr(mask), stream())
+        y, mask = dropout_fwd(x, p, seed, offset)
         ctx.save_for_backward(mask)
         ctx.p = p
         return y
@@ -306,11 +384,7 @@ class _DropoutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (mask,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(dy)
-        call("mmdx_dropout_bwd", L.dtype_code(dy.dtype), ptr(dy), ptr(mask), dy.numel(),
-             float(ctx.p), ptr(dx), stream())
-        return dx, None, None, None
+        return dropout_bwd(dy.contiguous(), mask, ctx.p), None, None, None
 
 
 def dropout(x, p, training):

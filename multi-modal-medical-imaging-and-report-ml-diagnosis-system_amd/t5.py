@@ -26,17 +26,6 @@ from . import functional as F
 from ._lib import call, ptr, stream
 
 
-def _cat_cast(ws, T, dev):
-    rows = sum(w.shape[0] for w in ws)
-    out = torch.empty((rows,) + tuple(ws[0].shape[1:]), dtype=T, device=dev)
-    o = 0
-    for w in ws:
-        n = w.shape[0]
-        call("mmdx_cast", L.dtype_code(T), L.F32, ptr(w), w.numel(), ptr(out[o:o + n]), stream())
-        o += n
-    return out
-
-
 def _mm(a, w, M, N, K, out, act=L.ACT_NONE, alpha=1.0, beta=0.0):
     """out[M,N] = act(alpha * a[M,K] @ w[N,K]^T) + beta * out."""
     return F.gemm(a, K, True, w, K, True, M, N, K, out, N, act=act, alpha=alpha, beta=beta,
@@ -77,29 +66,14 @@ def _rms_bwd(x, dy, w, r, dx_acc):
     return dw
 
 
-def _add(a, b):
-    out = torch.empty_like(a)
-    call("mmdx_add", L.dtype_code(a.dtype), a.numel(), ptr(a), ptr(b), ptr(out), stream())
-    return out
-
-
 def _dropout(x, p, training, seed):
     if not training or p <= 0.0:
         return x, None
-    y = torch.empty_like(x)
-    m = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    call("mmdx_dropout_fwd", L.dtype_code(x.dtype), ptr(x), x.numel(), float(p),
-         L.dropout_seed(seed), 0, ptr(L.rng_counter(x.device)), ptr(y), ptr(m), stream())
-    return y, m
+    return F.dropout_fwd(x, p, L.dropout_seed(seed))
 
 
 def _dropout_bwd(dy, m, p):
-    if m is None:
-        return dy
-    dx = torch.empty_like(dy)
-    call("mmdx_dropout_bwd", L.dtype_code(dy.dtype), ptr(dy), ptr(m), dy.numel(), float(p),
-         ptr(dx), stream())
-    return dx
+    return dy if m is None else F.dropout_bwd(dy, m, p)
 
 
 _SEED = [0x7A5]
@@ -129,7 +103,7 @@ class _T5BlockFn(torch.autograd.Function):
         keep = any(ctx.needs_input_grad)
         # --- self-attention: x + dropout(o(attn(rms(x))))
         n1, r1 = _rms(x, ln0, cfg.eps)
-        wqkv = _cat_cast([wq, wk, wv], T, dev)
+        wqkv = F.cat_cast([wq, wk, wv], T, dev)
         qkv = _mm(n1, wqkv, M, 3 * D, D, torch.empty((M, 3 * D), dtype=T, device=dev))
         att = torch.empty((M, D), dtype=T, device=dev)
         probs = torch.empty((B, H, Ls, Ls), dtype=torch.float32, device=dev) if keep else None
@@ -143,13 +117,13 @@ class _T5BlockFn(torch.autograd.Function):
         a = _mm(att, woc, M, D, D, torch.empty((M, D), dtype=T, device=dev))
         _SEED[0] += 1
         a, m1 = _dropout(a, cfg.p, tr, _SEED[0])
-        h1 = _add(x, a)
+        h1 = F.add(x, a)
         # --- cross-attention over the condition tokens
         n2, r2 = _rms(h1, ln1, cfg.eps)
         wq2c = F.cast(wq2, T)
         q2 = _mm(n2, wq2c, M, D, D, torch.empty((M, D), dtype=T, device=dev))
         e2 = enc.reshape(B * Kc, D)
-        wkv2 = _cat_cast([wk2, wv2], T, dev)
+        wkv2 = F.cat_cast([wk2, wv2], T, dev)
         kv = _mm(e2, wkv2, B * Kc, 2 * D, D, torch.empty((B * Kc, 2 * D), dtype=T, device=dev))
         xatt = torch.empty((M, D), dtype=T, device=dev)
         xprobs = torch.empty((B, H, Ls, Kc), dtype=torch.float32, device=dev) if keep else None
@@ -162,7 +136,7 @@ class _T5BlockFn(torch.autograd.Function):
         c = _mm(xatt, wo2c, M, D, D, torch.empty((M, D), dtype=T, device=dev))
         _SEED[0] += 1
         c, m2 = _dropout(c, cfg.p, tr, _SEED[0])
-        h2 = _add(h1, c)
+        h2 = F.add(h1, c)
         # --- FFN: h2 + dropout(wo(dropout(relu(wi(rms(h2))))))
         n3, r3 = _rms(h2, ln2, cfg.eps)
         I = wi.shape[0]
@@ -174,7 +148,7 @@ class _T5BlockFn(torch.autograd.Function):
         g = _mm(fd, wo3c, M, D, I, torch.empty((M, D), dtype=T, device=dev))
         _SEED[0] += 1
         g, m4 = _dropout(g, cfg.p, tr, _SEED[0])
-        h3 = _add(h2, g)
+        h3 = F.add(h2, g)
         if keep:
             ctx.save_for_backward(x, n1, r1, wqkv, qkv, probs, att, woc, h1, n2, r2, wq2c, q2,
                                   e2, wkv2, kv, xprobs, xatt, wo2c, h2, n3, r3, wic, f, fd, wo3c,
@@ -356,11 +330,11 @@ class _DecodeState:
         for blk in head._blocks():
             sa, ca, ff = blk.layer[0], blk.layer[1], blk.layer[2]
             at, xt = sa.SelfAttention, ca.EncDecAttention
-            wkv2 = _cat_cast([xt.k.weight, xt.v.weight], T, dev)
+            wkv2 = F.cat_cast([xt.k.weight, xt.v.weight], T, dev)
             kv = _mm(e2, wkv2, R * Kc, 2 * D, D, torch.empty((R * Kc, 2 * D), dtype=T, device=dev))
             self.blocks.append(dict(
-                ln0=sa.layer_norm.weight.detach(), wqkv=_cat_cast([at.q.weight, at.k.weight,
-                                                                   at.v.weight], T, dev),
+                ln0=sa.layer_norm.weight.detach(), wqkv=F.cat_cast([at.q.weight, at.k.weight,
+                                                                    at.v.weight], T, dev),
                 wo=F.cast(at.o.weight, T), ln1=ca.layer_norm.weight.detach(),
                 wq2=F.cast(xt.q.weight, T), kv=kv, wo2=F.cast(xt.o.weight, T),
                 ln2=ff.layer_norm.weight.detach(), wi=F.cast(ff.DenseReluDense.wi.weight, T),

@@ -4,14 +4,19 @@ tower; BASELINE config C5).
 Each stack (all of its layers) is ONE autograd node, like the ResNet trunk (resnet._TrunkFn):
 its forward and its backward are recorded once per (shape, dtype, mode, parameter set) as
 op lists over a persistent buffer arena (include/mmdx.h launch plans, csrc/plan.cpp) and
-replayed by one native call per step.  The eager per-layer nodes (bert._BertLayerFn,
-vit._VitBlockFn) issue the same kernels in the same order from Python — ~35 ctypes calls and
-~30 allocations per layer and direction, 32 ms of host time per C5 step, most of the step;
-here the host cost per stack and direction is one call plus the launches themselves.
+replayed by one native call per step.  The layers themselves are written once, in xlayers
+(bert_fwd / bert_bwd, vit_fwd / vit_bwd), over a recorder interface: _Rec here records their
+calls as plan ops, xlayers.Eager (behind bert._BertLayerFn, vit._VitBlockFn) issues them at
+once from Python — ~35 ctypes calls and ~30 allocations per layer and direction, 32 ms of
+host time per C5 step, most of the step; here the host cost per stack and direction is one
+call plus the launches themselves.
 
-Same arithmetic as the eager nodes (the plan-vs-eager tests require bit-identical outputs
-and gradients with dropout off).  Dropout draws from the per-device launch counter
-(_lib.rng_counter) under a seed fixed per plan op, so every replay draws fresh masks.
+Same body, so the same kernels with the same operands in the same order as the eager nodes
+(the plan-vs-eager tests require bit-identical outputs and gradients with dropout off;
+tools/plan_dump.py --stacks diffs two revisions' plans on the CPU).  What differs is in the
+back-end methods: weight casts hoisted into one launch, backward temporaries shared across
+layers, gradients at offsets of one flat buffer.  Dropout draws from the per-device launch
+counter (_lib.rng_counter) under a seed fixed per plan op, so every replay draws fresh masks.
 Per-call buffers enter as external bases: the stack input and the attention mask (forward),
 the upstream gradient, the parameter-gradient arena and the mask (backward).  The parameter
 gradients are views of one flat fp32 buffer per backward (the data-parallel reducer finds it
@@ -22,16 +27,15 @@ from __future__ import annotations
 import math
 import os
 import weakref
+from types import SimpleNamespace
 
 import torch
 
 from . import _lib as L
 from . import functional as F
+from . import xlayers as XL
 from .plan import WS, _Arena, _Ext, _OpList, _Token, pack_multi_args, plan_cache_get
 
-# ViT backward: residual-branch gradient added inside the LayerNorm backward (1, default) or
-# by a separate add pass (0); read by vit.py's eager path too
-VIT_LN_ADDIN = os.environ.get("MMDX_VIT_LN_ADDIN", "1") == "1"
 _F32 = torch.float32
 
 
@@ -45,11 +49,36 @@ class _Rec:
 
     def __init__(self, arena, T, ops):
         self.arena, self.T, self.ops = arena, T, ops
+        self.dev = arena.dev
         self.dt = L.dtype_code(T)
         self.ws_need = 0
+        self.packs = []
+        self.shared = {}
 
     def buf(self, shape, dtype=None):
         return self.arena.new(shape, dtype or self.T)
+
+    def scratch(self, name, shape):
+        """A backward temporary: one per name, shared by all the layers."""
+        if name not in self.shared:
+            self.shared[name] = self.buf(shape)
+        return self.shared[name]
+
+    def weights(self, ws):
+        """Compute-dtype copy of the fp32 masters, concatenated along dim 0; the casts are
+        queued for the head of the forward (flush_weight_casts)."""
+        dst = self.buf((sum(w.shape[0] for w in ws),) + tuple(ws[0].shape[1:]))
+        o = 0
+        for w in ws:
+            self.cast_weight(w, dst[o:o + w.shape[0]])
+            o += w.shape[0]
+        return dst
+
+    def seed(self, base, li):
+        """A dropout seed fixed per plan op (every replay draws fresh masks from the device
+        launch counter), as the signed 64-bit value a plan field holds."""
+        v = L.dropout_seed(base + 7919 * li)
+        return v - (1 << 64) if v >= (1 << 63) else v
 
     def _ws(self, n):
         self.ws_need = max(self.ws_need, int(n))
@@ -63,14 +92,13 @@ class _Rec:
         """fp32 [K][C] master -> compute-dtype copy; every one of the stack's is cast by ONE
         multi-tensor launch at the head of the forward (flush_weight_casts)."""
         K, Cc = w.shape[0], w.numel() // w.shape[0]
-        self.packs = getattr(self, "packs", []) + [(w, dst, None, K, Cc, Cc, 1)]
+        self.packs.append((w, dst, None, K, Cc, Cc, 1))
 
     def flush_weight_casts(self):
-        packs = getattr(self, "packs", [])
-        if not packs:
+        if not self.packs:
             return
         head = _OpList()
-        head.add(L.OP_CONV_PACK_MULTI, self.dt, **pack_multi_args(self.arena, packs))
+        head.add(L.OP_CONV_PACK_MULTI, self.dt, **pack_multi_args(self.arena, self.packs))
         self.ops.prepend(head)
 
     def copy(self, src, dst, n):
@@ -79,14 +107,15 @@ class _Rec:
     def axpby(self, n, a, x, b, y, out):
         self.ops.add(L.OP_AXPBY, i=(), l=(n,), f=(a, b), p=(x, y, out))
 
-    def gemm(self, A, lda, akm, B, ldb, bkm, M, N, K, C, ldc, c_dtype, bias=None, act=0,
-             preact=None, beta=0.0, residual=None):
-        """residual: a [M][ldc] tensor of C's dtype added last (mmdx_gemm_res)."""
+    def gemm(self, A, lda, akm, B, ldb, bkm, M, N, K, C, ldc, bias=None, act=0, preact=None,
+             beta=0.0, residual=None):
+        """C (compute dtype) = act(A B^T + bias) + beta C; residual: a [M][ldc] tensor of
+        C's dtype added last (mmdx_gemm_res)."""
         n = L.lib().mmdx_gemm_workspace_size(self.dt, M, N, K)
-        self.ops.timed(F.gemm_cost(M, N, K, self.dt, L.dtype_code(c_dtype),
+        self.ops.timed(F.gemm_cost(M, N, K, self.dt, self.dt,
                                    1.0 if residual is not None else beta, act, preact),
                        L.OP_GEMM, dtype=self.dt,
-                       i=(M, N, K, int(akm), int(bkm), L.dtype_code(c_dtype), act),
+                       i=(M, N, K, int(akm), int(bkm), self.dt, act),
                        l=(lda, ldb, ldc, n), f=(1.0, beta),
                        p=(A, B, C, bias, None, preact, self._ws(n), residual))
 
@@ -120,16 +149,24 @@ class _Rec:
         self.ops.add(L.OP_ATTN_BWD, self.dt, i=(B, Ls, H), f=(scale, p_drop), l=(n,),
                      p=(qkv, saved[1], dout, mask, dqkv, self._ws(n)))
 
-    def ln_fwd(self, x, res, g, b, eps, rows, D, y, xsum, mean, rstd):
+    def ln_fwd(self, x, res, g, b, eps, rows, D, want_sum=True):
+        """LayerNorm(x (+ res)) -> (y, x + res or None, mean, rstd)."""
+        y = self.buf((rows, D))
+        xsum = self.buf((rows, D)) if want_sum else None
+        mean, rstd = self.buf((rows,), _F32), self.buf((rows,), _F32)
         self.ops.add(L.OP_LN_FWD, self.dt, i=(D,), l=(rows,), f=(eps,),
                      p=(x, res, g, b, y, xsum, mean, rstd))
+        return y, xsum, mean, rstd
 
-    def ln_fwd_drop(self, x, res, g, b, eps, p, seed, counter, rows, D, y, xsum, mean, rstd):
-        """LayerNorm(dropout(x) + res); returns the dropout stream base buffer (rng)."""
+    def ln_fwd_drop(self, x, res, g, b, eps, p, seed, rows, D):
+        """LayerNorm(dropout(x) + res) -> (y, xsum, mean, rstd, rng): rng is the dropout
+        stream base buffer."""
+        y, xsum = self.buf((rows, D)), self.buf((rows, D))
+        mean, rstd = self.buf((rows,), _F32), self.buf((rows,), _F32)
         rng = self.buf((1,), torch.int64)
         self.ops.add(L.OP_LN_FWD_DROP, self.dt, i=(D,), l=(rows, seed), f=(eps, p),
-                     p=(x, res, g, b, y, xsum, mean, rstd, counter, rng))
-        return rng
+                     p=(x, res, g, b, y, xsum, mean, rstd, L.rng_counter(self.dev), rng))
+        return y, xsum, mean, rstd, rng
 
     def ln_bwd_drop(self, xsum, dy, g, mean, rstd, p, rng, rows, D, dx, dx_drop, dg, db):
         n = L.lib().mmdx_layernorm_workspace_size(rows, D)
@@ -227,241 +264,69 @@ def _plans_for(owner, key, build):
     return plan_cache_get(cache, key, build)
 
 
-def _seed(base):
-    """A dropout seed for a plan op, as the signed 64-bit value a plan field holds."""
-    v = L.dropout_seed(base)
-    return v - (1 << 64) if v >= (1 << 63) else v
+def _lay_out(G, base, table):
+    """Append one layer's gradients (xlayers.bert_grads / vit_grads; base = index of the
+    layer's first parameter) to the flat buffer -> {name: operand}."""
+    gd = {}
+    for name, idx, shape in table:
+        if isinstance(idx, tuple):   # row blocks of one fused buffer
+            off = G.take(shape)
+            n = math.prod(shape) // len(idx)
+            for j, i in enumerate(idx):
+                G.items.append((base + i, (shape[0] // len(idx),) + shape[1:], off + j * n))
+        else:
+            off = G.take(shape, base + idx)
+        gd[name] = G.ext(off)
+    return gd
 
 
-# ------------------------------------------------------------------------ BERT encoder
-# per layer, in bert.BertLayer.params() order:
-# wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2
-_BERT_NP = 16
-
-
-def _build_bert(params, B, Ls, D, Hn, I, eps, p, pa, T, dev):
-    pl = _StackPlan(dev, T)
-    M = B * Ls
-    scale = 1.0 / math.sqrt(D // Hn)
-    counter = L.rng_counter(dev)
-    nl = len(params) // _BERT_NP
-    rf = _Rec(pl.arena, T, pl.fwd)
-    x = _Ext(0)
-    mask = _Ext(1)
-    saves = []
+def _build(pl, params, npl, table, c, fwd, bwd, mask_fwd, mask_bwd):
+    """Record a stack of layers: fwd(be, li, x, mask, layer params, c) -> (out, saved) and
+    bwd(be, saved, dout, mask, gd, c) -> dx are the bodies the eager nodes run too.
+    Forward externals: 0 = the stack input [M, D], 1 = mask.  Backward externals: 0 = the
+    upstream gradient [M, D] (compute dtype), 1 = the gradient buffer, 2 = mask, 3 = the
+    stack input."""
+    nl = len(params) // npl
+    rf = _Rec(pl.arena, pl.T, pl.fwd)
+    x, saves = _Ext(0), []
     for li in range(nl):
-        (wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2,
-         b2) = params[li * _BERT_NP:(li + 1) * _BERT_NP]
-        wqkv = rf.buf((3 * D, D))
-        for j, w in enumerate((wq, wk, wv)):
-            rf.cast_weight(w, wqkv[j * D:(j + 1) * D])
-        bqkv = rf.buf((3 * D,), _F32)
-        for j, bb in enumerate((bq, bk, bv)):
-            rf.axpby(D, 1.0, bb, 0.0, None, bqkv[j * D:(j + 1) * D])
-        qkv = rf.buf((M, 3 * D))
-        rf.gemm(x, D, True, wqkv, D, True, M, 3 * D, D, qkv, 3 * D, T, bias=bqkv)
-        att = rf.buf((M, D))
-        probs = rf.attn_fwd(qkv, mask, B, Ls, Hn, scale, pa,
-                            _seed(0xA770 + 7919 * li) if pa > 0 else 0, counter, att)
-        woc = rf.buf((D, D))
-        rf.cast_weight(wo, woc)
-        a = rf.buf((M, D))
-        rf.gemm(att, D, True, woc, D, True, M, D, D, a, D, T, bias=bo)
-        # BertSelfOutput: LayerNorm(dropout(a) + x), the dropout inside the LayerNorm pass
-        # (no dropped tensor, no mask: the backward redraws the keep bits from rng)
-        m1 = None
-        h1, xs1 = rf.buf((M, D)), rf.buf((M, D))
-        mu1, rs1 = rf.buf((M,), _F32), rf.buf((M,), _F32)
-        if p > 0:
-            m1 = rf.ln_fwd_drop(a, x, g1, b1, eps, p, _seed(0xD401 + 7919 * li), counter, M, D,
-                                h1, xs1, mu1, rs1)
-        else:
-            rf.ln_fwd(a, x, g1, b1, eps, M, D, h1, xs1, mu1, rs1)
-        wic = rf.buf((I, D))
-        rf.cast_weight(wi, wic)
-        f, pre = rf.buf((M, I)), rf.buf((M, I))
-        rf.gemm(h1, D, True, wic, D, True, M, I, D, f, I, T, bias=bi, act=L.ACT_GELU,
-                preact=pre)
-        wo2c = rf.buf((D, I))
-        rf.cast_weight(wo2, wo2c)
-        f2 = rf.buf((M, D))
-        rf.gemm(f, I, True, wo2c, I, True, M, D, I, f2, D, T, bias=bo2)
-        m2 = None
-        h2, xs2 = rf.buf((M, D)), rf.buf((M, D))
-        mu2, rs2 = rf.buf((M,), _F32), rf.buf((M,), _F32)
-        if p > 0:   # BertOutput: LayerNorm(dropout(f2) + h1)
-            m2 = rf.ln_fwd_drop(f2, h1, g2, b2, eps, p, _seed(0xD402 + 7919 * li), counter, M,
-                                D, h2, xs2, mu2, rs2)
-        else:
-            rf.ln_fwd(f2, h1, g2, b2, eps, M, D, h2, xs2, mu2, rs2)
-        saves.append(dict(x=x, wqkv=wqkv, qkv=qkv, probs=probs, att=att, woc=woc, xs1=xs1,
-                          mu1=mu1, rs1=rs1, h1=h1, wic=wic, pre=pre, f=f, wo2c=wo2c, xs2=xs2,
-                          mu2=mu2, rs2=rs2, m1=m1, m2=m2))
-        x = h2
+        x, s = fwd(rf, li, x, mask_fwd, params[li * npl:(li + 1) * npl], c)
+        saves.append(s)
+    saves[0]["x"] = _Ext(3)
     pl.out = x
     rf.flush_weight_casts()
 
-    # backward: ext 0 = upstream gradient [M, D] (compute dtype), 1 = gradient buffer,
-    # 2 = mask.  Shared temporaries across layers; Y carries d(layer output) downward.
-    rb = _Rec(pl.arena, T, pl.bwd)
-    mask = _Ext(2)
-    X, Y = rb.buf((M, D)), rb.buf((M, D))
-    DX2 = rb.buf((M, D)) if p > 0 else None
-    DY1 = rb.buf((M, D)) if p > 0 else None
-    dpre = rb.buf((M, I))
-    datt, dqkv = rb.buf((M, D)), rb.buf((M, 3 * D))
+    rb = _Rec(pl.arena, pl.T, pl.bwd)
     G = pl.grads
-    offs = []
-    for li in range(nl):  # gradient layout in forward order
-        base = li * _BERT_NP
-        o = {}
-        o["wqkv"] = G.take((3 * D, D))
-        for j in range(3):
-            G.items.append((base + 2 * j, (D, D), o["wqkv"] + j * D * D))
-        o["bqkv"] = G.take((3 * D,))
-        for j in range(3):
-            G.items.append((base + 2 * j + 1, (D,), o["bqkv"] + j * D))
-        for name, idx, shape in (("wo", 6, (D, D)), ("bo", 7, (D,)), ("g1", 8, (D,)),
-                                 ("b1", 9, (D,)), ("wi", 10, (I, D)), ("bi", 11, (I,)),
-                                 ("wo2", 12, (D, I)), ("bo2", 13, (D,)), ("g2", 14, (D,)),
-                                 ("b2", 15, (D,))):
-            o[name] = G.take(shape, base + idx)
-        offs.append(o)
-    gx = G.ext
-    dh = _Ext(0)
+    starts = [G.n]   # first gradient element of each layer, then the buffer's end
+    gds = []
+    for li in range(nl):   # gradient layout in forward order
+        gds.append(_lay_out(G, li * npl, table))
+        starts.append(G.n)
+    d = _Ext(0)
     for li in range(nl - 1, -1, -1):
-        s, o = saves[li], offs[li]
-        g1 = params[li * _BERT_NP + 8]
-        g2 = params[li * _BERT_NP + 14]
-        dX2 = X
-        if p > 0:
-            rb.ln_bwd_drop(s["xs2"], dh, g2, s["mu2"], s["rs2"], p, s["m2"], M, D, X, DX2,
-                           gx(o["g2"]), gx(o["b2"]))
-            dX2 = DX2
-        else:
-            rb.ln_bwd(s["xs2"], dh, g2, s["mu2"], s["rs2"], M, D, X, gx(o["g2"]), gx(o["b2"]))
-        rb.gemm(dX2, D, True, s["wo2c"], I, False, M, I, D, dpre, I, T, act=L.ACT_GELU_BWD,
-                preact=s["pre"])
-        rb.gemm_wgrad_bias(dX2, D, s["f"], I, D, I, M, gx(o["wo2"]), I, gx(o["bo2"]))
-        rb.gemm_wgrad_bias(dpre, I, s["h1"], D, I, D, M, gx(o["wi"]), D, gx(o["bi"]))
-        rb.gemm(dpre, I, True, s["wic"], D, False, M, D, I, X, D, T, beta=1.0)
-        dY1 = Y
-        if p > 0:
-            rb.ln_bwd_drop(s["xs1"], X, g1, s["mu1"], s["rs1"], p, s["m1"], M, D, Y, DY1,
-                           gx(o["g1"]), gx(o["b1"]))
-            dY1 = DY1
-        else:
-            rb.ln_bwd(s["xs1"], X, g1, s["mu1"], s["rs1"], M, D, Y, gx(o["g1"]), gx(o["b1"]))
-        rb.gemm(dY1, D, True, s["woc"], D, False, M, D, D, datt, D, T)
-        rb.gemm_wgrad_bias(dY1, D, s["att"], D, D, D, M, gx(o["wo"]), D, gx(o["bo"]))
-        rb.attn_bwd(s["qkv"], s["probs"], s["att"], datt, mask, B, Ls, Hn, scale, pa, dqkv)
-        xin = s["x"] if not isinstance(s["x"], _Ext) else _Ext(3)  # the stack input
-        rb.gemm_wgrad_bias(dqkv, 3 * D, xin, D, 3 * D, D, M, gx(o["wqkv"]), D, gx(o["bqkv"]))
-        rb.gemm(dqkv, 3 * D, True, s["wqkv"], D, False, M, D, 3 * D, Y, D, T, beta=1.0)
-        dh = Y
-        pl.cut_after_layers(li, nl, lambda j: offs[j]["wqkv"] if j < nl else G.n)
-    pl.dx = Y
+        d = bwd(rb, saves[li], d, mask_bwd, gds[li], c)
+        pl.cut_after_layers(li, nl, starts.__getitem__)
+    pl.dx = d
     pl.finish((rf, rb))
     return pl
 
 
-# ------------------------------------------------------------------------ ViT encoder
-# per block, in vit.EncoderBlock order:
-# g1, b1, w_in, b_in, w_out, b_out, g2, b2, w1, bb1, w2, bb2
+# parameters per layer: bert.BertLayer.params() / vit.EncoderBlock order
+_BERT_NP = 16
 _VIT_NP = 12
 
 
-def _build_vit(params, N, S, D, heads, I, eps, T, dev):
-    pl = _StackPlan(dev, T)
-    M = N * S
-    scale = 1.0 / math.sqrt(D // heads)
-    nl = len(params) // _VIT_NP
-    rf = _Rec(pl.arena, T, pl.fwd)
-    x = _Ext(0)
-    saves = []
-    for li in range(nl):
-        g1, b1, w_in, b_in, w_out, b_out, g2, b2, w1, bb1, w2, bb2 = \
-            params[li * _VIT_NP:(li + 1) * _VIT_NP]
-        u1, mu1, rs1 = rf.buf((M, D)), rf.buf((M,), _F32), rf.buf((M,), _F32)
-        rf.ln_fwd(x, None, g1, b1, eps, M, D, u1, None, mu1, rs1)
-        wqkv = rf.buf((3 * D, D))
-        rf.cast_weight(w_in, wqkv)
-        qkv = rf.buf((M, 3 * D))
-        rf.gemm(u1, D, True, wqkv, D, True, M, 3 * D, D, qkv, 3 * D, T, bias=b_in)
-        att = rf.buf((M, D))
-        probs = rf.attn_fwd(qkv, None, N, S, heads, scale, 0.0, 0, None, att)
-        woc = rf.buf((D, D))
-        rf.cast_weight(w_out, woc)
-        o_ = rf.buf((M, D))
-        rf.gemm(att, D, True, woc, D, True, M, D, D, o_, D, T, bias=b_out)
-        u2, a = rf.buf((M, D)), rf.buf((M, D))
-        mu2, rs2 = rf.buf((M,), _F32), rf.buf((M,), _F32)
-        rf.ln_fwd(o_, x, g2, b2, eps, M, D, u2, a, mu2, rs2)
-        w1c = rf.buf((I, D))
-        rf.cast_weight(w1, w1c)
-        f, pre = rf.buf((M, I)), rf.buf((M, I))
-        rf.gemm(u2, D, True, w1c, D, True, M, I, D, f, I, T, bias=bb1, act=L.ACT_GELU,
-                preact=pre)
-        w2c = rf.buf((D, I))
-        rf.cast_weight(w2, w2c)
-        out = rf.buf((M, D))   # out = a + f W2^T + b2, the residual read by the epilogue
-        rf.gemm(f, I, True, w2c, I, True, M, D, I, out, D, T, bias=bb2, residual=a)
-        saves.append(dict(x=x, u1=u1, mu1=mu1, rs1=rs1, wqkv=wqkv, qkv=qkv, probs=probs,
-                          att=att, woc=woc, a=a, u2=u2, mu2=mu2, rs2=rs2, w1c=w1c, pre=pre,
-                          f=f, w2c=w2c))
-        x = out
-    pl.out = x
-    rf.flush_weight_casts()
+def _build_bert(params, B, Ls, D, Hn, I, eps, p, pa, T, dev):
+    c = SimpleNamespace(B=B, Ls=Ls, D=D, H=Hn, I=I, eps=eps, p=p, pa=pa)
+    return _build(_StackPlan(dev, T), params, _BERT_NP, XL.bert_grads(D, I), c, XL.bert_fwd,
+                  XL.bert_bwd, _Ext(1), _Ext(2))
 
-    # backward: ext 0 = upstream gradient, 1 = gradient buffer, 3 = the stack input
-    rb = _Rec(pl.arena, T, pl.bwd)
-    dpre = rb.buf((M, I))
-    du2, DA, da_ln = rb.buf((M, D)), rb.buf((M, D)), rb.buf((M, D))
-    datt, dqkv, du1 = rb.buf((M, D)), rb.buf((M, 3 * D)), rb.buf((M, D))
-    DX = rb.buf((M, D))
-    G = pl.grads
-    offs = []
-    for li in range(nl):
-        base = li * _VIT_NP
-        shapes = ((D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,), (I, D), (I,),
-                  (D, I), (D,))
-        offs.append([G.take(sh, base + j) for j, sh in enumerate(shapes)])
-    gx = G.ext
-    dO = _Ext(0)
-    for li in range(nl - 1, -1, -1):
-        s, o = saves[li], offs[li]
-        g1 = params[li * _VIT_NP + 0]
-        g2 = params[li * _VIT_NP + 6]
-        rb.gemm(dO, D, True, s["w2c"], I, False, M, I, D, dpre, I, T, act=L.ACT_GELU_BWD,
-                preact=s["pre"])
-        rb.gemm_wgrad_bias(dO, D, s["f"], I, D, I, M, gx(o[10]), I, gx(o[11]))
-        rb.gemm_wgrad_bias(dpre, I, s["u2"], D, I, D, M, gx(o[8]), D, gx(o[9]))
-        rb.gemm(dpre, I, True, s["w1c"], D, False, M, D, I, du2, D, T)
-        # da = dO + LN2'(du2): the residual branch's gradient added inside the LN backward
-        # (mmdx_layernorm_bwd_residual; MMDX_VIT_LN_ADDIN=0: a separate add pass).  Within the
-        # box-to-box spread on C5: -0.8 % and +1.2 % against the add pass on two boxes, paired
-        # (profiles/r04_c5_ab_ln_addin.txt)
-        if VIT_LN_ADDIN:
-            rb.ln_bwd(s["a"], du2, g2, s["mu2"], s["rs2"], M, D, DA, gx(o[6]), gx(o[7]), addin=dO)
-        else:
-            rb.ln_bwd(s["a"], du2, g2, s["mu2"], s["rs2"], M, D, da_ln, gx(o[6]), gx(o[7]))
-            rb.add(dO, da_ln, M * D, DA)
-        rb.gemm(DA, D, True, s["woc"], D, False, M, D, D, datt, D, T)
-        rb.gemm_wgrad_bias(DA, D, s["att"], D, D, D, M, gx(o[4]), D, gx(o[5]))
-        rb.attn_bwd(s["qkv"], s["probs"], s["att"], datt, None, N, S, heads, scale, 0.0, dqkv)
-        rb.gemm_wgrad_bias(dqkv, 3 * D, s["u1"], D, 3 * D, D, M, gx(o[2]), D, gx(o[3]))
-        rb.gemm(dqkv, 3 * D, True, s["wqkv"], D, False, M, D, 3 * D, du1, D, T)
-        xin = s["x"] if not isinstance(s["x"], _Ext) else _Ext(3)
-        if VIT_LN_ADDIN:
-            rb.ln_bwd(xin, du1, g1, s["mu1"], s["rs1"], M, D, DX, gx(o[0]), gx(o[1]), addin=DA)
-        else:
-            rb.ln_bwd(xin, du1, g1, s["mu1"], s["rs1"], M, D, da_ln, gx(o[0]), gx(o[1]))
-            rb.add(DA, da_ln, M * D, DX)
-        dO = DX
-        pl.cut_after_layers(li, nl, lambda j: offs[j][0] if j < nl else G.n)
-    pl.dx = DX
-    pl.finish((rf, rb))
-    return pl
+
+def _build_vit(params, N, S, D, heads, I, eps, T, dev):
+    c = SimpleNamespace(B=N, Ls=S, D=D, H=heads, I=I, eps=eps)
+    return _build(_StackPlan(dev, T), params, _VIT_NP, XL.vit_grads(D, I), c, XL.vit_fwd,
+                  XL.vit_bwd, None, None)
 
 
 # ------------------------------------------------------------------------ autograd node

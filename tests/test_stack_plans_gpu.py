@@ -24,8 +24,7 @@ pytestmark = pytest.mark.gpu
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 
 
-def _bert_run(dev, dt, plans, monkeypatch, p=0.0, steps=1):
-    monkeypatch.setenv("MMDX_STACK_PLANS", "1" if plans else "0")
+def _bert_setup(dev, dt, p=0.0):
     torch.manual_seed(3)
     m = MB.BertModel.from_name("bert-base-uncased@2")
     m.config.hidden_dropout_prob = p
@@ -38,6 +37,15 @@ def _bert_run(dev, dt, plans, monkeypatch, p=0.0, steps=1):
     mask[1, 20:] = 0
     mask = mask.to(dev)
     w = torch.randn(3, 37, 768, generator=g).to(dev)
+    return m, ids, mask, w
+
+
+def _bert_run(dev, dt, plans, monkeypatch, p=0.0, steps=1, prep=None):
+    """prep(m): called on the model before the first step (to freeze a parameter)."""
+    monkeypatch.setenv("MMDX_STACK_PLANS", "1" if plans else "0")
+    m, ids, mask, w = _bert_setup(dev, dt, p)
+    if prep is not None:
+        prep(m)
     outs = []
     for _ in range(steps):
         for q in m.parameters():
@@ -85,18 +93,26 @@ def test_bert_plan_gradients_tile_one_buffer(dev, monkeypatch):
     assert sum(g.numel() for g in enc) * 4 == enc[0].untyped_storage().nbytes()
 
 
-def _vit_run(dev, dt, plans, monkeypatch):
-    monkeypatch.setenv("MMDX_STACK_PLANS", "1" if plans else "0")
+def _vit_setup(dev, dt):
     torch.manual_seed(0)
     m = VitTrunk(layers=2)
     m.compute_dtype = dt
     m.to(dev)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 3, 224, 224, generator=g).to(dev)
+    return m, x, g
+
+
+def _vit_run(dev, dt, plans, monkeypatch, prep=None):
+    monkeypatch.setenv("MMDX_STACK_PLANS", "1" if plans else "0")
+    m, x, g = _vit_setup(dev, dt)
+    if prep is not None:
+        prep(m)
     f = m(x)
     dy = torch.randn(f.shape, generator=g).to(dev)
     f.float().backward(dy)
-    return f.detach().clone(), {n: q.grad.detach().clone() for n, q in m.named_parameters()}
+    return f.detach().clone(), {n: q.grad.detach().clone() for n, q in m.named_parameters()
+                                if q.requires_grad}
 
 
 @pytest.mark.parametrize("dt", DTYPES)
@@ -106,6 +122,57 @@ def test_vit_stack_plan_matches_eager(dev, dt, monkeypatch):
     assert torch.equal(f0, f1)
     bad = [n for n in g0 if not torch.equal(g0[n], g1[n])]
     assert not bad, bad
+
+
+def _frozen(run, dev, dt, monkeypatch, name):
+    """The stack with parameter `name` frozen (plans on) against the all-trainable plan run:
+    no plan is built (xplan.run_stack returns None, the eager nodes run with gradients on and
+    everything kept for their backward), and with dropout off the output and every remaining
+    parameter gradient are bit-identical."""
+    seen = []
+
+    def freeze(m):
+        dict(m.named_parameters())[name].requires_grad_(False)
+        seen.append(m)
+    h0, g0 = run(dev, dt, True, monkeypatch, prep=freeze)
+    h1, g1 = run(dev, dt, True, monkeypatch, prep=seen.append)
+    plans = [m.encoder.__dict__.get("_mmdx_stack_plans") for m in seen]
+    assert not plans[0], "plan built with a frozen parameter"
+    assert plans[1], "the all-trainable run built no plan"
+    assert torch.equal(h0, h1)
+    assert set(g0) == set(g1) - {name}
+    bad = [n for n in g0 if not torch.equal(g0[n], g1[n])]
+    assert not bad, bad
+
+
+def test_bert_frozen_parameter_runs_eager_nodes(dev, monkeypatch):
+    def run(*a, **k):
+        return _bert_run(*a, **k)[0]
+    _frozen(run, dev, torch.bfloat16, monkeypatch,
+            "encoder.layer.0.attention.output.LayerNorm.weight")
+
+
+def test_vit_frozen_parameter_runs_eager_nodes(dev, monkeypatch):
+    _frozen(_vit_run, dev, torch.float16, monkeypatch,
+            "encoder.layers.encoder_layer_0.ln_1.weight")
+
+
+def test_no_grad_forward_matches_eager_forward(dev, monkeypatch):
+    """fp32 (both routes use mmdx_attention_fwd): the forward under no_grad, which keeps
+    nothing for a backward, is bit-identical to the grad-enabled eager forward."""
+    monkeypatch.setenv("MMDX_STACK_PLANS", "0")
+    m, ids, mask, _ = _bert_setup(dev, torch.float32)
+    h = m(input_ids=ids, attention_mask=mask).last_hidden_state
+    assert h.requires_grad
+    with torch.no_grad():
+        h_ng = m(input_ids=ids, attention_mask=mask).last_hidden_state
+    assert torch.equal(h.detach(), h_ng)
+    v, x, _ = _vit_setup(dev, torch.float32)
+    f = v(x)
+    assert f.requires_grad
+    with torch.no_grad():
+        f_ng = v(x)
+    assert torch.equal(f.detach(), f_ng)
 
 
 def test_stack_plan_not_used_without_grad(dev, monkeypatch):

@@ -2,10 +2,14 @@
 CPU tensors standing in for device memory (nothing is launched): the parameter-gradient
 layout tiles one flat buffer exactly (what the data-parallel reducer relies on), every
 weight is cast by the single multi-tensor launch at the head of the forward, the workspace
-placeholder is patched everywhere, and the op mix per layer is the eager node's.  The
-plans' arithmetic is checked on the GPU against the eager nodes (test_stack_plans_gpu.py).
+placeholder is patched everywhere, and the op mix per layer is the expected one.  The plans
+record the layer bodies that the eager nodes issue call by call (mmdx.xlayers); that the two
+back-ends agree bit for bit is checked on the GPU (test_stack_plans_gpu.py).  The eager
+one-op wrappers exist once, in mmdx.functional (test_eager_helpers_exist_once).
 """
+import ast
 import math
+import os
 
 import pytest
 import torch
@@ -111,6 +115,30 @@ def test_plan_cache_evicts_idle_stale_keys(monkeypatch):
     assert len(cache) <= 3 and "k0" not in cache and "k4" in cache
     again = PL.plan_cache_get(cache, "k4", _P)
     assert again is cache["k4"][0]          # an idle plan of the key is reused
+
+
+def test_eager_helpers_exist_once():
+    """The eager one-op wrappers live in mmdx.functional only: no module defines a _cat_cast
+    of its own, and mmdx_layernorm_bwd is called from exactly one Python function of the
+    package (the _residual and _dropout variants are names of their own)."""
+    import mmdx
+    pkg = os.path.dirname(mmdx.__file__)
+    callers = []
+    for fn in sorted(os.listdir(pkg)):
+        if not fn.endswith(".py"):
+            continue
+        with open(os.path.join(pkg, fn)) as f:
+            src = f.read()
+        assert "_cat_cast" not in src, f"{fn} has a _cat_cast of its own"
+        for node in ast.walk(ast.parse(src)):
+            if not isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef)):
+                continue
+            for sub in ast.walk(node):
+                named = (isinstance(sub, ast.Constant) and sub.value == "mmdx_layernorm_bwd") \
+                    or (isinstance(sub, ast.Attribute) and sub.attr == "mmdx_layernorm_bwd")
+                if named:
+                    callers.append(f"{fn}:{node.name}")
+    assert callers == ["functional.py:ln_bwd"], callers
 
 
 def _small_vit_params(nl, D=64, I=128):
