@@ -773,6 +773,27 @@ int mmdx_cam_fwd(int dtype, const void* fmap, const float* alpha, int B, int HW,
 int mmdx_cam_resize(const float* raw, int BC, int H, int W, int Ho, int Wo, int normalize,
                     float* out, void* stream);
 
+/* ---------------------------------------------------------------- training augmentation
+ * Per-image affine warp + contrast / brightness of normalised images, one launch, no workspace,
+ * no atomics, bit-reproducible.  x, out fp32 [B][C][H][W] (NCHW, contiguous, out must not
+ * overlap x); params fp32 [B][8] on the DEVICE, row b = (a00, a01, ox, a10, a11, oy, gain,
+ * delta); mean, stdv: HOST arrays of C floats (the normalisation x carries, stdv > 0).
+ *
+ * With cx = (W-1)/2, cy = (H-1)/2, dx = j - cx, dy = i - cy, output pixel (i, j) samples the
+ * source position sx = a00 dx + a01 dy + (cx + ox), sy = a10 dx + a11 dy + (cy + oy) (pixel
+ * index coordinates) as the bilinear blend of the four taps (floor(sy) | +1, floor(sx) | +1);
+ * a tap outside the image reads fill_c = (0 - mean_c) / std_c (black).  The blend weights are
+ * exactly 1 and 0 at integer positions, so identity / flip / quarter-turn / whole-pixel-shift
+ * rows return input bits.  sx, sy are clamped in floating point to [-1.5, size + 0.5] before
+ * the conversion to int (all taps are outside there anyway): any parameter row is safe.
+ * Then v' = gain v + ((gain - 1)(mean_c - 0.5) + delta) / std_c, i.e. the pixel-space
+ * p' = gain (p - 0.5) + 0.5 + delta, and with clamp != 0 v' is clamped to
+ * [(0 - mean_c) / std_c, (1 - mean_c) / std_c], the fp32 values mmdx_image_preprocess writes
+ * for the pixel values 0 and 255.  Limits: 1 <= C <= 4, H, W <= 4096, B <= 65535. */
+int mmdx_augment_affine(const float* x, const float* params, int B, int C, int H, int W,
+                        const float* mean, const float* stdv, int clamp, float* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

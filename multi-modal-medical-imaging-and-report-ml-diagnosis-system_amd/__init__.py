@@ -12,5 +12,6 @@ from .training_pipeline import (  # noqa: F401
 from .optim import AdamW, clip_grad_norm_  # noqa: F401
 from .amp import GradScaler  # noqa: F401
 from .preprocess import preprocess_batch  # noqa: F401
+from .augment import Augment  # noqa: F401
 
 __version__ = "0.1.0"

@@ -212,6 +212,8 @@ SIGNATURES = {
     "mmdx_confusion_grid": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     "mmdx_cam_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "mmdx_augment_affine": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),
+                                  i32, vp, vp]),
 }
 
 _lib = None

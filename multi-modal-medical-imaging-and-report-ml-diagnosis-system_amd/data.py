@@ -17,6 +17,7 @@ Reference behaviour kept:
 New: `LocalCXRBatches` decodes a batch on the host with PIL (as the reference does) and runs
 the transform for the whole batch on the GPU in two HIP launches (`preprocess_batch`,
 bit-exact with `image_transfom_into_tensor`), so the host cost per sample is the decode.
+With `augment=` one more launch warps and re-exposes the batch there (mmdx.augment).
 """
 from __future__ import annotations
 
@@ -123,10 +124,12 @@ class LocalCXRBatches:
     are decoded on the host (PIL, TP:146) and transformed on the GPU for the whole batch
     (`preprocess_batch`, identical to stacking `image_transfom_into_tensor` outputs).
     `shuffle` draws a seeded permutation per epoch; the last partial batch is kept unless
-    `drop_last`."""
+    `drop_last`.  `augment` (an mmdx.augment.Augment, training only) is applied to every batch
+    on the GPU after the transform; it draws from its own Generator, so the shuffle order is the
+    one without it, and None yields the transform's output untouched."""
 
     def __init__(self, df, image_root, batch_size=32, shuffle=True, seed=0, drop_last=False,
-                 device=None):
+                 device=None, augment=None):
         self.keys, self.labels = construct_input_label_pairs_for_image_encoder_dataset(df)
         self.details = df["patient_details"].astype(str).tolist()
         self.image_root = image_root
@@ -135,6 +138,7 @@ class LocalCXRBatches:
         self.rng = np.random.default_rng(seed)
         self.drop_last = drop_last
         self.device = device
+        self.augment = augment
 
     def __len__(self):
         n = len(self.keys)
@@ -156,5 +160,7 @@ class LocalCXRBatches:
                 break
             imgs = [open_image(self.image_root, self.keys[i]) for i in idx]
             x = preprocess_batch(imgs, dev)
+            if self.augment is not None:
+                x = self.augment(x)
             y = torch.from_numpy(np.stack([self.labels[i] for i in idx])).to(dev)
             yield x, [self.details[i] for i in idx], y

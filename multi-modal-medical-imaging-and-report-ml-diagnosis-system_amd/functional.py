@@ -17,6 +17,7 @@ from ._lib import call, ptr, stream
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
+    "augment_affine",
 ]
 
 
@@ -559,4 +560,49 @@ def cam_resize(raw, out_size, normalize=True):
     out = torch.empty((*raw.shape[:-2], Ho, Wo), dtype=torch.float32, device=raw.device)
     call("mmdx_cam_resize", ptr(raw), raw.numel() // (H * W) if H * W else 0, H, W, Ho, Wo,
          int(bool(normalize)), ptr(out), stream())
+    return out
+
+
+# ----------------------------------------------------------------------------- augmentation
+def augment_affine(x, params, mean=None, std=None, clamp=True, out=None):
+    """Per-image affine warp (bilinear, black outside) + contrast / brightness of the
+    normalised fp32 NCHW batch x [B, C, H, W], in one launch (mmdx_augment_affine; the
+    semantics are those of mmdx.augment, whose `reference` is the CPU statement of them).
+    params: CPU [B, 8] fp32 tensor or ndarray, row = (a00, a01, ox, a10, a11, oy, gain, delta),
+    validated on the host (augment.check_params) and then uploaded.  mean / std: the
+    normalisation x carries (default: preprocess_batch's ImageNet constants).  clamp=False
+    skips the clamp to the normalised [0, 1] pixel range.  Returns `out` (a new tensor unless
+    given), which must not share memory with x.  C <= 4, H, W <= 4096, B <= 65535.  A wrong
+    dtype, layout, shape or an aliasing `out` is a ValueError, never a hidden copy."""
+    import ctypes
+    from . import augment as A
+    if x.dtype != torch.float32:
+        raise ValueError(f"augment_affine takes fp32 images, got {x.dtype}")
+    if x.dim() != 4:
+        raise ValueError(f"augment_affine takes [B, C, H, W], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("augment_affine takes a contiguous NCHW tensor")
+    B, C, H, W = x.shape
+    if not (1 <= C <= A.MAX_C and 1 <= H <= A.MAX_HW and 1 <= W <= A.MAX_HW
+            and 1 <= B <= A.MAX_B):
+        raise ValueError(f"augment_affine: shape {tuple(x.shape)} outside 1 <= B <= {A.MAX_B}, "
+                         f"C <= {A.MAX_C}, H, W <= {A.MAX_HW}")
+    if out is not None:
+        if out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or \
+                out.device != x.device:
+            raise ValueError("augment_affine: out must be a contiguous fp32 tensor of x's shape "
+                             "on x's device")
+        nbytes = x.numel() * 4
+        if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("augment_affine: out must not alias x (the warp is a gather)")
+    rows = A.check_params(params, B)
+    m, s = A.norm_constants(C, mean, std)
+    L.require_device(x)
+    if out is None:
+        out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        d_rows = torch.from_numpy(rows).to(x.device)
+        call("mmdx_augment_affine", ptr(x), ptr(d_rows), B, C, H, W,
+             (ctypes.c_float * C)(*m.tolist()), (ctypes.c_float * C)(*s.tolist()),
+             int(bool(clamp)), ptr(out), stream())
     return out

@@ -152,7 +152,8 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
-                   model_name="fusion_model_T5", device=None, verbose=True, val_rows=0):
+                   model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
+                   augment=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -162,7 +163,12 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     - the image tower's warm-up batches draw from the whole frame either way), evaluates on
     them after the fusion phase (mmdx.metrics.evaluate, with report generation under the run's
     gen_kwargs), returns that dict as out["val"], and registers its val_auroc_micro / _macro,
-    val_loss, val_f1_micro and val_rougeL (nan stored as None) with the chosen thresholds."""
+    val_loss, val_f1_micro and val_rougeL (nan stored as None) with the chosen thresholds.
+
+    augment (an mmdx.augment.Augment, default None = the reference's run) is handed to the
+    image tower's training batches only: the fusion phase encodes its images once with frozen
+    towers and stays unaugmented, and validation batches never augment.  Data-parallel ranks
+    pass Augments with different seeds (for example seed + rank)."""
     from PIL import Image
     from . import training_pipeline as TP
     from .data import LocalCXRBatches
@@ -184,7 +190,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
 
     log("----------IMAGE ENCODER: DATASET / BATCHES----------")
     batches = LocalCXRBatches(df, _image_root_for(df), batch_size=batch_size, shuffle=True,
-                              device=dev)
+                              device=dev, augment=augment)
     imgs, _, y = next(iter(batches))
     log(f"batch img input shape: {tuple(imgs.shape)}, labels {tuple(y.shape)}")
 
