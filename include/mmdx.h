@@ -491,6 +491,44 @@ int mmdx_bce_logits_fwd(const float* logits, const float* target, int B, int C,
 int mmdx_bce_logits_bwd(const float* logits, const float* target, int B, int C,
                         const float* dloss, float* dlogits, void* stream);
 
+/* Disease loss: BCE-with-logits with pos_weight, class weights, ignored labels, label smoothing
+ * and focal modulation, for imbalanced and partly labelled targets (no counterpart in the
+ * reference, which trains with the plain loss above).  logits [B][C] in `dtype` (fp32, bf16 or
+ * fp16), target fp32 [B][C]; a NaN target means "no label" (mask m = 0), any other target is a
+ * label in [0, 1].  pos_weight / class_weight: fp32 [C] on the device, or NULL for all ones.
+ * All arithmetic is fp32.  Per element, with eps = label_smoothing:
+ *   y' = y (1 - eps) + eps / 2,  p = sigmoid(z),
+ *   bce = pw_c y' softplus(-z) + (1 - y') softplus(z)        (softplus in the max-shifted form),
+ *   e   = m cw_c |y' - p|^gamma bce                          (gamma == 0: no pow, factor 1),
+ *   g   = de/dz = m cw_c [gamma |d|^(gamma-1) sign(d) p (1-p) bce
+ *                         + |d|^gamma ((1 - y') p - pw_c y' (1 - p))],   d = p - y'.
+ * gamma is 0 or >= 1 (for 0 < gamma < 1 the gradient is unbounded at p = y').
+ *
+ * mmdx_disease_loss_fwd, ONE kernel launch (plus a 16-byte memset of the ticket counter when the
+ * grid has more than one block), no host sync, no float atomics:
+ *   stats fp32 [C][2]: per class (sum_b e, sum_b m);
+ *   norm[0]: max(sum m, 1) with mean != 0 (the mean over LABELLED elements), 1 otherwise (sum);
+ *   loss[0] = sum e / norm[0] - an all-ignored batch gives 0, never NaN;
+ *   g fp32 [B][C] (NULL: no gradient wanted): the UN-normalised element gradient; exactly +0
+ *   where the label is ignored.
+ * mmdx_disease_loss_bwd: dlogits[i] (in `dtype`) = g[i] * (dloss[0] / norm[0]), rounded once;
+ * dloss (NULL = 1) and norm are device scalars, so a scaled loss back-propagates with no sync.
+ * The grid grows with B * C; per-block partial sums go through the workspace
+ * (mmdx_disease_loss_workspace_size(B, C) bytes, 16-byte aligned; 0 for illegal B, C) and are
+ * added by the last block in block order: loss, stats and g are bit-reproducible run to run.
+ * Finite for every finite logit whose loss term is representable in fp32 (cw pw |z| below
+ * FLT_MAX); g is finite and bounded by cw (gamma + 1) max(pw, 1) for ANY finite logit.
+ * Argument errors: C > 64, B * C > 2^31 - 1, gamma or label_smoothing out of range, a NULL or
+ * unaligned required pointer, a short workspace, outputs that overlap an input or each other. */
+size_t mmdx_disease_loss_workspace_size(long B, int C);
+int mmdx_disease_loss_fwd(int dtype, const void* logits, const float* target, long B, int C,
+                          const float* pos_weight, const float* class_weight, float gamma,
+                          float label_smoothing, int mean, float* loss, float* stats,
+                          float* norm, float* g, void* workspace, size_t ws_bytes,
+                          void* stream);
+int mmdx_disease_loss_bwd(int dtype, const float* g, long n, const float* dloss,
+                          const float* norm, void* dlogits, void* stream);
+
 /* ---------------------------------------------------------------- text towers
  * BERT embeddings: word[id] + pos[i] + type[tt] -> LayerNorm (transformers BertEmbeddings,
  * reached from TextEncoderTransformer.encode TP:470/473).  ids/tt int64 [B,L]. */

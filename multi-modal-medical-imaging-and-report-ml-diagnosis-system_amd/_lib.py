@@ -153,6 +153,10 @@ SIGNATURES = {
     "mmdx_dropout_bwd": (i32, [i32, vp, vp, i64, f32, vp, vp]),
     "mmdx_bce_logits_fwd": (i32, [vp, vp, i32, i32, vp, vp]),
     "mmdx_bce_logits_bwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "mmdx_disease_loss_workspace_size": (sz, [i64, i32]),
+    "mmdx_disease_loss_fwd": (i32, [i32, vp, vp, i64, i32, vp, vp, f32, f32, i32, vp, vp, vp, vp,
+                                    vp, sz, vp]),
+    "mmdx_disease_loss_bwd": (i32, [i32, vp, i64, vp, vp, vp, vp]),
     "mmdx_embed_ln_fwd": (i32, [i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp,
                                 vp, vp]),
     "mmdx_embed_bwd": (i32, [i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),

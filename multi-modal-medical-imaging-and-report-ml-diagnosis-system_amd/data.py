@@ -86,6 +86,77 @@ def construct_input_label_pairs_for_image_encoder_dataset(df):
     return keys, labels
 
 
+def _label_matrix(df_or_labels):
+    """[N, C] float array from a feature dataframe (its disease_classification_vector column)
+    or from the labels themselves (an array or a list of rows)."""
+    if hasattr(df_or_labels, "columns"):
+        df_or_labels = list(df_or_labels["disease_classification_vector"])
+    a = np.asarray(df_or_labels, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"labels must be [N, C], got shape {a.shape}")
+    return a
+
+
+def label_stats(df_or_labels):
+    """Per-class label counts of a feature dataframe or an [N, C] label array, as int64 [C]
+    arrays in a dict: n_pos (label > 0.5), n_neg (0 <= label <= 0.5), n_uncertain (-1),
+    n_missing (NaN), and n (rows).  CheXpert-style frames carry all four kinds."""
+    a = _label_matrix(df_or_labels)
+    nan = np.isnan(a)
+    unc = a == -1.0
+    pos = a > 0.5
+    neg = ~nan & ~unc & ~pos
+    return {"n": int(a.shape[0]),
+            "n_pos": pos.sum(0).astype(np.int64), "n_neg": neg.sum(0).astype(np.int64),
+            "n_uncertain": unc.sum(0).astype(np.int64), "n_missing": nan.sum(0).astype(np.int64)}
+
+
+def pos_weight_from_stats(stats, cap=20.0):
+    """BCE pos_weight per class from label_stats(): min(n_neg / n_pos, cap), and 1 where a class
+    has no positives.  float32 [C], ready for mmdx.DiseaseLoss(pos_weight=...)."""
+    if not (cap > 0.0 and np.isfinite(cap)):
+        raise ValueError(f"cap must be finite and > 0, got {cap}")
+    n_pos = np.asarray(stats["n_pos"], dtype=np.float64)
+    n_neg = np.asarray(stats["n_neg"], dtype=np.float64)
+    w = np.ones_like(n_pos)
+    has = n_pos > 0
+    w[has] = np.minimum(n_neg[has] / n_pos[has], cap)
+    return w.astype(np.float32)
+
+
+def apply_uncertain(labels, policy):
+    """Map the uncertain (-1) labels of an [N, C] array by `policy`:
+    None leaves `labels` untouched (the same object is returned, nothing is checked);
+    "ignore" maps -1 to NaN (no label: the disease loss and evaluate() leave it out);
+    "zeros" / "ones" map -1 to 0 / 1; a float u in (0, 1) maps -1 to the soft label u.
+    NaN (not mentioned) stays NaN under every policy.  Returns a new float32 array.  Any value
+    outside {-1, NaN} and [0, 1] is a ValueError naming the row and the class."""
+    if policy is None:
+        return labels
+    if isinstance(policy, str):
+        fill = {"ignore": np.nan, "zeros": 0.0, "ones": 1.0}.get(policy)
+        if fill is None:
+            raise ValueError(f"uncertain policy {policy!r}: None, 'ignore', 'zeros', 'ones' or "
+                             "a float in (0, 1)")
+    elif isinstance(policy, (int, float, np.floating)) and not isinstance(policy, bool):
+        fill = float(policy)
+        if not (0.0 < fill < 1.0):
+            raise ValueError(f"uncertain policy {policy}: a soft label must be in (0, 1)")
+    else:
+        raise ValueError(f"uncertain policy {policy!r}: None, 'ignore', 'zeros', 'ones' or a "
+                         "float in (0, 1)")
+    a = np.array(labels, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"labels must be [N, C], got shape {a.shape}")
+    unc = a == -1.0
+    bad = ~(np.isnan(a) | unc | ((a >= 0.0) & (a <= 1.0)))
+    if bad.any():
+        r, c = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f"label {a[r, c]!r} at row {r}, class {c} is not -1, NaN or in [0, 1]")
+    a[unc] = fill
+    return a
+
+
 def open_image(root, key):
     """Image bytes -> PIL image (TP:144-146), from `root/key` (or `key` if absolute)."""
     from PIL import Image
@@ -126,11 +197,15 @@ class LocalCXRBatches:
     `shuffle` draws a seeded permutation per epoch; the last partial batch is kept unless
     `drop_last`.  `augment` (an mmdx.augment.Augment, training only) is applied to every batch
     on the GPU after the transform; it draws from its own Generator, so the shuffle order is the
-    one without it, and None yields the transform's output untouched."""
+    one without it, and None yields the transform's output untouched.  `uncertain` is an
+    apply_uncertain() policy for -1 labels, applied once here; None (default) yields the stored
+    label values bit for bit."""
 
     def __init__(self, df, image_root, batch_size=32, shuffle=True, seed=0, drop_last=False,
-                 device=None, augment=None):
+                 device=None, augment=None, uncertain=None):
         self.keys, self.labels = construct_input_label_pairs_for_image_encoder_dataset(df)
+        if uncertain is not None and self.labels:
+            self.labels = list(apply_uncertain(np.stack(self.labels), uncertain))
         self.details = df["patient_details"].astype(str).tolist()
         self.image_root = image_root
         self.batch_size = int(batch_size)

@@ -17,7 +17,7 @@ from ._lib import call, ptr, stream
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
-    "augment_affine",
+    "augment_affine", "disease_loss",
 ]
 
 
@@ -422,6 +422,78 @@ class _BCEFn(torch.autograd.Function):
 
 def bce_with_logits(logits, target):
     return _BCEFn.apply(logits.contiguous(), target.contiguous())
+
+
+# ----------------------------------------------------------------------------- disease loss
+class _DiseaseLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, pw, cw, gamma, eps, mean):
+        B, Cn = logits.shape
+        dev = logits.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        norm = torch.empty(1, dtype=torch.float32, device=dev)
+        stats = torch.empty((Cn, 2), dtype=torch.float32, device=dev)
+        want = ctx.needs_input_grad[0]
+        g = torch.empty((B, Cn), dtype=torch.float32, device=dev) if want else None
+        n = L.lib().mmdx_disease_loss_workspace_size(B, Cn)
+        ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        call("mmdx_disease_loss_fwd", L.dtype_code(logits.dtype), ptr(logits), ptr(target), B,
+             Cn, ptr(pw), ptr(cw), gamma, eps, int(mean), ptr(loss), ptr(stats), ptr(norm),
+             ptr(g), ptr(ws), n, stream())
+        if want:
+            ctx.save_for_backward(g, norm)
+        ctx.dt = logits.dtype
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        g, norm = ctx.saved_tensors
+        dloss = dloss.contiguous().float()
+        dz = torch.empty(g.shape, dtype=ctx.dt, device=g.device)
+        call("mmdx_disease_loss_bwd", L.dtype_code(ctx.dt), ptr(g), g.numel(), ptr(dloss),
+             ptr(norm), ptr(dz), stream())
+        return dz, None, None, None, None, None, None
+
+
+def disease_loss(logits, target, pos_weight=None, class_weight=None, gamma=0.0,
+                 label_smoothing=0.0, reduction="mean"):
+    """(loss, stats) of the weighted / masked / smoothed / focal BCE defined in mmdx.losses:
+    logits [B, C] fp32, bf16 or fp16; target fp32 [B, C] with NaN = "no label"; pos_weight and
+    class_weight fp32 [C] on the logits' device (or None).  stats [C, 2] (per-class loss sum and
+    labelled count) stays on the device.  One forward launch; the backward scales the saved
+    element gradient by the device scalars dloss / normaliser (no sync, GradScaler-safe) and
+    rounds once to the logits' dtype.  Every argument is checked on the host first: ValueError /
+    TypeError, never a copy behind the caller's back (a non-contiguous input is an error)."""
+    from .losses import MAX_CLASSES, check_loss_args, check_weight
+    gamma, eps = check_loss_args(gamma, label_smoothing, reduction)
+    if not torch.is_tensor(logits) or not torch.is_tensor(target):
+        raise TypeError("disease_loss: logits and target must be tensors")
+    if logits.dim() != 2 or target.shape != logits.shape:
+        raise ValueError(f"disease_loss: logits {tuple(logits.shape)} and target "
+                         f"{tuple(target.shape)} must both be [B, C]")
+    B, Cn = logits.shape
+    if B < 1 or Cn < 1 or Cn > MAX_CLASSES or B * Cn > 2 ** 31 - 1:
+        raise ValueError(f"disease_loss: [B, C] = [{B}, {Cn}] outside 1 <= C <= {MAX_CLASSES}, "
+                         "1 <= B * C <= 2^31 - 1")
+    check_weight("pos_weight", pos_weight, Cn)
+    check_weight("class_weight", class_weight, Cn)
+    if logits.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError(f"disease_loss: logits must be float32, bfloat16 or float16, got "
+                        f"{logits.dtype}")
+    if target.dtype != torch.float32:
+        raise TypeError(f"disease_loss: target must be float32, got {target.dtype}")
+    for name, t in (("logits", logits), ("target", target), ("pos_weight", pos_weight),
+                    ("class_weight", class_weight)):
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError(f"disease_loss: {name} is not contiguous (it is never copied here)")
+        if not t.is_cuda or t.device != logits.device:
+            raise ValueError(f"disease_loss: {name} is on {t.device}; every tensor must be on "
+                             "the logits' GPU (there is no CPU path)")
+    return _DiseaseLossFn.apply(logits, target, pos_weight, class_weight, gamma, eps,
+                                reduction == "mean")
 
 
 # ----------------------------------------------------------------------------- pooling

@@ -182,7 +182,7 @@ def _append_rows(buf, n, rows):
 
 def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=None,
              grid_probs=None, generate=False, gen_kwargs=None, report_labels=None,
-             compute_dtype=None):
+             compute_dtype=None, criterion=None):
     """Validation metrics of the three modules over `batches`, an iterable of
     (images, patient_details, labels) as data.LocalCXRBatches yields them.
 
@@ -195,6 +195,12 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     patient_details strings to the text encoder's inputs (default tokenize_patient_details,
     max_len 96); `compute_dtype` casts the embeddings handed to the fusion model (None: as the
     encoders produce them); `grid_probs` defaults to default_grid() and gets 0.5 added if absent.
+
+    `criterion` (an mmdx.DiseaseLoss) computes val_loss instead of the plain BCE; None keeps the
+    plain BCE, which is NaN if a label is.  Independently of it, an ignored label (NaN, see
+    data.apply_uncertain) is left out of AUROC, the threshold sweep and n_pos: its score is
+    masked on the device and the per-class counts of masked elements travel in the same copy.
+    A NaN the model produced at a labelled element still raises (auroc_from_counts).
 
     generate=True (needs the report head and `report_labels`, int64 [N, L] token ids in batch
     order, -100 / pad ignored) beam-generates a report per row with `gen_kwargs` and scores
@@ -249,11 +255,18 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
             if n == 0:
                 raise ValueError("evaluate: no validation rows")
             z, y = logits_buf[:n], labels_buf[:n]
-            loss = F.bce_with_logits(z, y)
-            counts = F.auroc_counts(z, y)
+            loss = F.bce_with_logits(z, y) if criterion is None else criterion(z, y)
+            # an ignored (NaN) label becomes a NaN score with target 0: the metrics kernels
+            # drop NaN scores and count them in n_nan, from which `ignored` is taken off below
+            ign = torch.isnan(y)
+            ignored = ign.sum(0)
+            zm = torch.where(ign, torch.full_like(z, math.nan), z)
+            ym = torch.where(ign, torch.zeros_like(y), y)
+            counts = F.auroc_counts(zm, ym)
             thr = torch.from_numpy(thr_host).to(z.device)
-            tp, fp = F.confusion_grid(z, y, thr)
+            tp, fp = F.confusion_grid(zm, ym, thr)
             packed = torch.cat([counts.reshape(-1), tp.reshape(-1), fp.reshape(-1),
+                                ignored.reshape(-1).to(torch.int64),
                                 loss.reshape(1).view(torch.int32).to(torch.int64)])
             host = packed.cpu().numpy()  # the one device-to-host copy
     finally:
@@ -261,9 +274,12 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
             m.training = was
 
     C, T = z.shape[1], len(grid)
-    k = host[:(C + 1) * 4].reshape(C + 1, 4)
+    k = host[:(C + 1) * 4].reshape(C + 1, 4).copy()
     tp_h = host[(C + 1) * 4:(C + 1) * 4 + C * T].reshape(C, T)
     fp_h = host[(C + 1) * 4 + C * T:(C + 1) * 4 + 2 * C * T].reshape(C, T)
+    ign_h = host[(C + 1) * 4 + 2 * C * T:(C + 1) * 4 + 2 * C * T + C]
+    k[:C, 3] -= ign_h            # what is left in n_nan is a NaN the model produced
+    k[C, 3] -= ign_h.sum()
     val_loss = float(np.array([host[-1]], dtype=np.int64).astype(np.int32).view(np.float32)[0])
     per_class, macro, micro = auroc_from_counts(k)
     # labels per class from the sweep-independent pair counts (no NaN got past the line above)

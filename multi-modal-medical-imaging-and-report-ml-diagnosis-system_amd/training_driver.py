@@ -153,7 +153,7 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
-                   augment=None):
+                   augment=None, criterion=None, uncertain=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -168,10 +168,18 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     augment (an mmdx.augment.Augment, default None = the reference's run) is handed to the
     image tower's training batches only: the fusion phase encodes its images once with frozen
     towers and stays unaugmented, and validation batches never augment.  Data-parallel ranks
-    pass Augments with different seeds (for example seed + rank)."""
+    pass Augments with different seeds (for example seed + rank).
+
+    criterion (an mmdx.DiseaseLoss, default None = the reference's BCEWithLogitsLoss()) replaces
+    the plain loss in the image-tower phases, the text phases and the fusion classification loss
+    (where it takes the fp16 logits as they are), computes val_loss, and has its config() stored
+    under artifacts["loss"]; without it the bundle is what it was.  uncertain (a
+    data.apply_uncertain policy, default None) maps the -1 labels of the training batches and of
+    the fusion rows; the validation loader then uses "ignore", so uncertain labels are left out
+    of the metrics.  NaN (missing) labels need a criterion: the plain loss returns NaN on them."""
     from PIL import Image
     from . import training_pipeline as TP
-    from .data import LocalCXRBatches
+    from .data import LocalCXRBatches, apply_uncertain
     from .inference_pipeline import DISEASES
 
     log = print if verbose else (lambda *a, **k: None)
@@ -190,14 +198,16 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
 
     log("----------IMAGE ENCODER: DATASET / BATCHES----------")
     batches = LocalCXRBatches(df, _image_root_for(df), batch_size=batch_size, shuffle=True,
-                              device=dev, augment=augment)
+                              device=dev, augment=augment, uncertain=uncertain)
     imgs, _, y = next(iter(batches))
     log(f"batch img input shape: {tuple(imgs.shape)}, labels {tuple(y.shape)}")
 
     log("---------IMAGE ENCODER: CREATE IMAGE-ENCODER-CLASS----------")
     model = TP.ImageEncoderCNN(backbone_name=image_backbone, d_img=1024,
                                n_disease_classes=13).to(dev)
-    criterion = TP.BCEWithLogitsLoss()
+    plain_loss = criterion is None
+    if plain_loss:
+        criterion = TP.BCEWithLogitsLoss()
     out["image_loss"] = []
     for phase in (1, 2):
         if phase == 1:
@@ -266,9 +276,10 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     rows = rows.reset_index(drop=True)
     from .preprocess import preprocess_batch
     imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev)
-    y_multi = torch.tensor(np.stack([np.asarray(v, dtype=np.float32)
-                                     for v in rows["disease_classification_vector"]]),
-                           dtype=torch.float32, device=dev)
+    y_multi = torch.tensor(apply_uncertain(
+        np.stack([np.asarray(v, dtype=np.float32)
+                  for v in rows["disease_classification_vector"]]), uncertain),
+        dtype=torch.float32, device=dev)
     tok_aligned = TP.tokenize_patient_details(rows["patient_details"].astype(str).tolist(),
                                               max_len=96)
     tok_aligned = {k: v.to(dev) for k, v in tok_aligned.items()}
@@ -305,7 +316,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         o = fusion_model(z_img=z_img.to(amp_dtype), z_txt=z_txt.to(amp_dtype),
                          report_input_ids=None, report_attention_mask=None,
                          report_labels=report_labels)
-        loss_cls = criterion(o["disease_logits"].float(), y_multi)
+        z_cls = o["disease_logits"]
+        loss_cls = criterion(z_cls.float() if plain_loss else z_cls, y_multi)
         loss_gen = o["gen"].loss if o["gen"] is not None else 0.0
         loss = loss_cls + 1.0 * loss_gen
         scaler.scale(loss).backward()                                     # TP:1056
@@ -346,8 +358,10 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         val_labels[val_rep["attention_mask"] == 0] = -100
         val = evaluate(image_encoder, text_encoder, fusion_model,
                        LocalCXRBatches(val_df, _image_root_for(val_df), batch_size=batch_size,
-                                       shuffle=False, device=dev),
-                       generate=True, gen_kwargs=gen, report_labels=val_labels)
+                                       shuffle=False, device=dev,
+                                       uncertain=None if uncertain is None else "ignore"),
+                       generate=True, gen_kwargs=gen, report_labels=val_labels,
+                       criterion=None if plain_loss else criterion)
         out["val"] = val
         metrics = {k: (None if v != v else v) for k, v in
                    ((k, val[k]) for k in ("val_auroc_micro", "val_auroc_macro", "val_loss",
@@ -359,12 +373,15 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             f"{val['val_rougeL']:.4f}")
 
     if save:
+        artifacts = {"class_names": list(DISEASES), "thresholds": thresholds}
+        if not plain_loss:
+            artifacts["loss"] = criterion.config()
         rm = save_model_to_hopsworks_model_registry(
             fusion_model=fusion_model, text_encoder=text_encoder, image_encoder=image_encoder,
             model_name=model_name, description="CXR fusion: CNN+Text -> MLP; multi-label "
                                                "disease head; T5 report head.",
             metrics=metrics,
-            artifacts={"class_names": list(DISEASES), "thresholds": thresholds},
+            artifacts=artifacts,
             t5_tokenizer=t5_tok, save_t5_weights=False, hf_model_name="t5-small")
         log("model version in registry:", rm.version)
         out["registry_version"] = rm.version
