@@ -791,6 +791,67 @@ int mmdx_auroc_pairs(const float* scores, const float* target, int N, int C, int
 int mmdx_confusion_grid(const float* logits, const float* target, int N, int C,
                         const float* thr, int T, int64_t* tp, int64_t* fp, void* stream);
 
+/* ---------------------------------------------------------------- calibration
+ * Post-hoc calibration of the disease probabilities: a monotone per-class map z' = a_c z + b_c,
+ * p = sigmoid(z'), fitted on held-out fp32 [N][C] logits and targets, and the reliability
+ * statistics that measure it.  The CPU statement (float64) is mmdx/calibration.py.
+ *
+ * mmdx_calib_fit_step is ONE pass of a damped-Newton (Levenberg-Marquardt) fit; a fit is
+ * iters + 1 calls on one stream, pass = 0 ... iters with last != 0 in the final one, all with
+ * the same arguments otherwise and the same workspace, which carries the solver state from pass
+ * to pass (mmdx_calib_fit_workspace_size(N, C) bytes, 16-byte aligned, no initialisation
+ * needed; 0 for illegal N, C).  No host sync, no data-dependent launch count, no float atomics.
+ *   mode MMDX_CALIB_PLATT: a free (a_c, b_c) per class; MMDX_CALIB_TEMPERATURE: one scalar a
+ *   for all classes, b = 0 (NLL, ga, haa summed over the classes in class order).
+ *   A NaN target means "no label" (m = 0), any other target is a label y in [0, 1].
+ *   counts fp64 [C][2] on the device: (n_pos_c, n_neg_c) = (sum m y, sum m (1 - y)).  With
+ *   smooth != 0 the targets are Platt's, t = t_neg + y (t_pos - t_neg), t_pos = (n_pos + 1) /
+ *   (n_pos + 2), t_neg = 1 / (n_neg + 2) (finite optimum on separable data); else t = y.
+ *   Objective: NLL_c = sum_i m (softplus(z') - t z').
+ * Per pass, one launch: z' = a z + b with (a, b) the trial point rounded to fp32, as a separate
+ * multiply and add (never an fma, so the host reproduces z' bit for bit); fp32 element terms
+ * (one max-shifted expf, one log1pf, 1 - p as sigmoid(-z')); the seven per-class sums (NLL, ga,
+ * gb, haa, hab, hbb, labelled count) in fp64 from the thread upward, through a fixed-order LDS
+ * tree and per-block partials that the last block (integer ticket) adds in block order:
+ * bit-reproducible.  The last block then takes the solver step in fp64: pass 0 evaluates
+ * (1, 0) with lambda = 1e-3; a trial point whose NLL is <= NLL_accepted (1 + 1e-9) is accepted
+ * and lambda /= 10 (floor 1e-9), else it is rejected and lambda *= 10 (cap 1e12); the next
+ * trial point is theta_acc - (H_acc with its diagonal scaled by (1 + lambda))^-1 g_acc.  It
+ * leaves the ticket counter at 0 for the next pass.
+ * The final pass (last != 0) evaluates the last trial point, and writes for the accepted point
+ *   status int32 [C]: 0 fitted; 1 inactive (n_pos < min_count or n_neg < min_count, or nothing
+ *     labelled); 2 not converged (Newton decrement g^T H^-1 g per labelled element > tol, or a
+ *     value not finite); 3 non-positive slope.  In temperature mode the pooled counts and sums
+ *     decide one status for all classes.
+ *   scale, bias fp32 [C]: (a_c, b_c) where status is 0, the identity (1, 0) elsewhere;
+ *   info fp64 [C][4]: NLL at the identity, NLL at the result, Newton decrement per labelled
+ *     element, labelled count (temperature mode: the pooled values, repeated per class).
+ * scale, bias, status and info may be NULL in the other passes.  pass = 0 with last != 0 is a
+ * plain evaluation of the NLL at the identity.  Argument errors: C > 64, N * C > 2^31 - 1, an
+ * unknown mode, min_count < 0, tol not in (0, inf), a NULL or unaligned required pointer, a
+ * short workspace, outputs that overlap an input or each other.
+ *
+ * mmdx_reliability_bins: the integer sufficient statistics of a reliability diagram with n_bins
+ * equal-width probability bins, 1 <= n_bins <= 64.  z' = z * scale[c] + bias[c] (an explicit
+ * multiply and add; scale = bias = NULL: z' = z exactly); edges fp32 [n_bins - 1], the interior
+ * bin edges in LOGIT space, non-decreasing (NULL allowed for n_bins = 1); the bin of an element
+ * is #{k : edges[k] <= z'}, so an edge belongs to the upper bin.  A target is positive iff
+ * target > 0.5; an element with a NaN z' is dropped and counted.  out int64, zeroed by the
+ * entry point: [(C + 1)][n_bins][4] = {count, positives, sum round(p 2^30),
+ * sum round((p - y)^2 2^30)} with p = sigmoid(z') in fp32 and y in {0, 1}, followed by
+ * [(C + 1)] NaN counts; row C pools all classes (micro).  Integer atomics only:
+ * bit-reproducible and exactly comparable with a CPU reference.  Limits as the validation
+ * metrics: C <= 64, N * C <= 2^24. */
+enum { MMDX_CALIB_TEMPERATURE = 0, MMDX_CALIB_PLATT = 1 };
+size_t mmdx_calib_fit_workspace_size(long N, int C);
+int mmdx_calib_fit_step(const float* logits, const float* target, long N, int C,
+                        const double* counts, int smooth, int mode, int pass, int last,
+                        long min_count, double tol, float* scale, float* bias, int* status,
+                        double* info, void* workspace, size_t ws_bytes, void* stream);
+int mmdx_reliability_bins(const float* logits, const float* target, int N, int C,
+                          const float* scale, const float* bias, const float* edges, int n_bins,
+                          int64_t* out, void* stream);
+
 /* ---------------------------------------------------------------- Grad-CAM
  * Heatmaps of the disease head at the trunk's last conv stage.  Between that feature map and
  * the logits there is only the global average pool and the heads, so the Grad-CAM channel

@@ -20,6 +20,7 @@ F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_BWD = 0, 1, 2, 3
 
 vp, i32, i64, f32, sz, u64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_uint64
+f64 = C.c_double
 
 
 class ConvDesc(C.Structure):
@@ -214,6 +215,10 @@ SIGNATURES = {
     "mmdx_mul_dev_scalar": (i32, [vp, i64, vp, vp, vp]),
     "mmdx_auroc_pairs": (i32, [vp, vp, i32, i32, vp, vp]),
     "mmdx_confusion_grid": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "mmdx_calib_fit_workspace_size": (sz, [i64, i32]),
+    "mmdx_calib_fit_step": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, i32, i64, f64, vp, vp, vp,
+                                  vp, vp, sz, vp]),
+    "mmdx_reliability_bins": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
     "mmdx_cam_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mmdx_augment_affine": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),

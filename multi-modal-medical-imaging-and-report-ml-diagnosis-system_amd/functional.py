@@ -17,7 +17,7 @@ from ._lib import call, ptr, stream
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
-    "augment_affine", "disease_loss",
+    "augment_affine", "disease_loss", "calib_fit", "reliability_bins",
 ]
 
 
@@ -594,6 +594,97 @@ def confusion_grid(logits, target, thr):
     call("mmdx_confusion_grid", ptr(logits), ptr(target), N, C, ptr(thr), T, ptr(tp), ptr(fp),
          stream())
     return tp, fp
+
+
+# ----------------------------------------------------------------------------- calibration
+def _calib_inputs(name, logits, target):
+    """_metric_inputs with the errors of an argument check: TypeError / ValueError before any
+    launch, never a hidden copy."""
+    if not torch.is_tensor(logits) or not torch.is_tensor(target):
+        raise TypeError(f"{name}: logits and target must be tensors")
+    if logits.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"{name} takes fp32 logits and targets, got {logits.dtype} and "
+                        f"{target.dtype}")
+    if logits.dim() != 2 or logits.shape != target.shape:
+        raise ValueError(f"{name} takes logits and targets of one shape [N, C], got "
+                         f"{tuple(logits.shape)} and {tuple(target.shape)}")
+    for what, t in (("logits", logits), ("target", target)):
+        if not t.is_cuda or t.device != logits.device:
+            raise ValueError(f"{name}: {what} is on {t.device}; every tensor must be on one GPU "
+                             "(there is no CPU path)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} is not contiguous (it is never copied here)")
+    return logits.shape
+
+
+def calib_fit(logits, target, mode="platt", iters=32, smooth=True, min_count=1, tol=1e-7):
+    """Fit the calibration map z' = a_c z + b_c of mmdx.calibration (mode "platt": per class;
+    "temperature": one scalar a, b = 0) on fp32 contiguous [N, C] logits and targets (NaN
+    target = no label) by damped Newton: iters + 1 launches of mmdx_calib_fit_step on the
+    current stream, no host sync.  Returns device tensors (scale fp32 [C], bias fp32 [C],
+    status int32 [C], info fp64 [C, 4]); scale / bias are the identity wherever status != 0
+    (mmdx.calibration: the status codes; info = NLL at the identity, NLL at the result, Newton
+    decrement per labelled element, labelled count).  iters = 0 evaluates the NLL at the
+    identity.  Bit-reproducible.  C <= 64, N * C <= 2^31 - 1."""
+    from .calibration import MAX_CLASSES, MODES, check_fit_args
+    tol = check_fit_args(mode, iters, min_count, tol)
+    N, C = _calib_inputs("calib_fit", logits, target)
+    if N < 1 or C < 1 or C > MAX_CLASSES or N * C > 2 ** 31 - 1:
+        raise ValueError(f"calib_fit: [N, C] = [{N}, {C}] outside 1 <= C <= {MAX_CLASSES}, "
+                         "1 <= N * C <= 2^31 - 1")
+    dev = logits.device
+    # the label counts of Platt's targets and of the min_count rule: torch ops, no sync
+    lab = ~torch.isnan(target)
+    n_lab = lab.sum(0, dtype=torch.float64)
+    n_pos = torch.where(lab, target, target.new_zeros(())).sum(0, dtype=torch.float64)
+    counts = torch.stack([n_pos, n_lab - n_pos], dim=1).contiguous()
+    scale = torch.empty(C, dtype=torch.float32, device=dev)
+    bias = torch.empty(C, dtype=torch.float32, device=dev)
+    status = torch.empty(C, dtype=torch.int32, device=dev)
+    info = torch.empty((C, 4), dtype=torch.float64, device=dev)
+    n = L.lib().mmdx_calib_fit_workspace_size(N, C)
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    code = MODES.index(mode)
+    st = stream()
+    for k in range(iters + 1):
+        call("mmdx_calib_fit_step", ptr(logits), ptr(target), N, C, ptr(counts), int(bool(smooth)),
+             code, k, int(k == iters), min_count, tol, ptr(scale), ptr(bias), ptr(status),
+             ptr(info), ptr(ws), n, st)
+    return scale, bias, status, info
+
+
+def reliability_bins(logits, target, scale=None, bias=None, n_bins=15):
+    """(bins, n_nan) of a reliability diagram with n_bins equal-width probability bins, from fp32
+    contiguous [N, C] logits and targets (positive iff > 0.5), optionally after the calibration
+    map z' = z * scale + bias (fp32 [C] device tensors, both or neither).  bins int64
+    [(C + 1), n_bins, 4] = (count, positives, sum round(p 2^30), sum round((p - y)^2 2^30)),
+    n_nan int64 [(C + 1)] the dropped NaN logits; row C is micro (mmdx_reliability_bins;
+    mmdx.calibration.calibration_from_bins turns them into ECE / MCE / Brier on the host).
+    Exact counts, bit-reproducible.  N * C <= 2^24, C <= 64, 1 <= n_bins <= 64."""
+    from .calibration import MAX_CLASSES, bin_edges
+    edges_host = bin_edges(n_bins)
+    N, C = _calib_inputs("reliability_bins", logits, target)
+    if N < 1 or C < 1 or C > MAX_CLASSES or N * C > 2 ** 24:
+        raise ValueError(f"reliability_bins: [N, C] = [{N}, {C}] outside 1 <= C <= "
+                         f"{MAX_CLASSES}, 1 <= N * C <= 2^24")
+    if (scale is None) != (bias is None):
+        raise ValueError("reliability_bins: scale and bias come together")
+    for what, t in (("scale", scale), ("bias", bias)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError(f"reliability_bins: {what} must be an fp32 tensor")
+        if t.shape != (C,) or not t.is_contiguous():
+            raise ValueError(f"reliability_bins: {what} must be contiguous [{C}], got "
+                             f"{tuple(t.shape)}")
+        if t.device != logits.device:
+            raise ValueError(f"reliability_bins: {what} is on {t.device}, the logits on "
+                             f"{logits.device}")
+    edges = torch.from_numpy(edges_host).to(logits.device) if n_bins > 1 else None
+    out = torch.empty((C + 1) * n_bins * 4 + (C + 1), dtype=torch.int64, device=logits.device)
+    call("mmdx_reliability_bins", ptr(logits), ptr(target), N, C, ptr(scale), ptr(bias),
+         ptr(edges), n_bins, ptr(out), stream())
+    return out[:(C + 1) * n_bins * 4].view(C + 1, n_bins, 4), out[(C + 1) * n_bins * 4:]
 
 
 # ----------------------------------------------------------------------------- Grad-CAM

@@ -7,7 +7,8 @@ function here, in float64 from exact integers, so it can be tested without a GPU
 - `auroc_from_counts`: Mann-Whitney AUROC (midranks for ties) per class, macro and micro;
 - `pick_thresholds`: per-class F1-optimal probability thresholds from a threshold sweep;
 - `rouge_l`: token-id ROUGE-L F1 of generated reports;
-- `evaluate`: the loop that feeds them from held-out batches.
+- `evaluate`: the loop that feeds them from held-out batches (and, with `calibrate`, fits and
+  measures a probability calibration: mmdx.calibration).
 
 `evaluate()` runs in ONE process: pair counts need every score on one rank, so data-parallel
 evaluation is out of scope (gather the logits to one rank first).  The AUROC kernel counts all
@@ -180,9 +181,50 @@ def _append_rows(buf, n, rows):
     return buf, need
 
 
+def _calibration_report(x, C, n_bins, ignored, mode):
+    """The "calibration" entry of evaluate() from the int64 words of the one host copy, in the
+    order evaluate() packed them."""
+    from . import calibration as K
+    nb = (C + 1) * n_bins * 4
+    sides, o = [], 0
+    for _ in range(2):
+        bins = x[o:o + nb].reshape(C + 1, n_bins, 4)
+        n_nan = x[o + nb:o + nb + C + 1].copy()
+        n_nan[:C] -= ignored        # what is left is a NaN the model produced
+        n_nan[C] -= ignored.sum()
+        sides.append(K.calibration_from_bins(bins, n_nan))
+        o += nb + C + 1
+
+    def f32(w):
+        return np.ascontiguousarray(w).astype(np.int32).view(np.float32)
+
+    scale, bias = f32(x[o:o + C]), f32(x[o + C:o + 2 * C])
+    status = [int(v) for v in x[o + 2 * C:o + 3 * C]]
+    o += 3 * C
+    nll = [np.ascontiguousarray(x[o + i * C:o + (i + 1) * C]).view(np.float64) for i in range(3)]
+    n_lab = nll[2]  # labelled elements per class (the evaluation passes run per class)
+
+    def side(rel, s):
+        tot = float(n_lab.sum())
+        d = {"val_nll_per_class": [float(v) / float(m) if m > 0 else math.nan
+                                   for v, m in zip(s, n_lab)],
+             "val_nll_micro": math.fsum(float(v) for v in s) / tot if tot > 0 else math.nan}
+        for k in ("ece", "mce", "brier"):
+            d[f"val_{k}_micro"] = rel["micro"][k]
+            d[f"val_{k}_per_class"] = [r[k] for r in rel["per_class"]]
+        keep = ("mean_p", "frac_pos", "count")
+        d["reliability"] = {"micro": {k: rel["micro"][k] for k in keep},
+                            "per_class": [{k: r[k] for k in keep} for r in rel["per_class"]]}
+        return d
+
+    out = K.to_dict(mode, scale, bias, status)
+    out.update(n_bins=n_bins, before=side(sides[0], nll[0]), after=side(sides[1], nll[1]))
+    return out
+
+
 def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=None,
              grid_probs=None, generate=False, gen_kwargs=None, report_labels=None,
-             compute_dtype=None, criterion=None):
+             compute_dtype=None, criterion=None, calibrate=None, n_bins=15):
     """Validation metrics of the three modules over `batches`, an iterable of
     (images, patient_details, labels) as data.LocalCXRBatches yields them.
 
@@ -206,6 +248,21 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     order, -100 / pad ignored) beam-generates a report per row with `gen_kwargs` and scores
     token-id ROUGE-L; generation syncs with the host per batch, the metric path does not.
 
+    `calibrate` (default None: today's launches, bits and keys) measures and repairs the
+    probabilities (mmdx.calibration).  "temperature" or "platt" fits that map on the collected
+    rows (functional.calib_fit); a calibration dict is applied without fitting, so a map fitted
+    on one split can be measured on another.  The result then gains "calibration": the dict
+    (mode, scale, bias) plus status, n_bins and, under "before" and "after", val_ece_micro /
+    _per_class, val_mce_*, val_brier_*, val_nll_* (the plain BCE of the labelled elements) and
+    "reliability" (per class and micro: mean_p, frac_pos and count per bin, `n_bins`
+    equal-width bins).  The threshold sweep then runs on the CALIBRATED logits, so `thresholds`
+    refer to the probabilities inference() reports from a bundle that carries the map; AUROC
+    stays on the raw logits (the map is monotone, and the identity where a class was not
+    fitted, so it is the uncalibrated number exactly).  Ignored labels are left out of the fit
+    and of the bins.  Everything new travels in the same single copy.  "after" numbers of a
+    map fitted on the same rows are IN-SAMPLE: they show what the map can do, not what it will
+    do on new data.
+
     Returns n, val_loss, val_auroc_micro, val_auroc_macro, val_auroc_per_class, thresholds,
     val_f1_micro (at the chosen thresholds), val_f1_micro_at_0p5, per_class (precision, recall,
     f1, n_pos, ...) and, with generate, val_rougeL.  Single process only (module docstring)."""
@@ -221,6 +278,16 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     has_head = getattr(fusion_model, "report_model", None) is not None
     if generate and has_head and report_labels is None:
         raise ValueError("evaluate(generate=True) needs report_labels")
+    if calibrate is not None:
+        from . import calibration as K
+        if isinstance(calibrate, str):
+            if calibrate not in K.MODES:
+                raise ValueError(f"evaluate: calibrate must be None, one of {K.MODES} or a "
+                                 f"calibration dict, got {calibrate!r}")
+        elif not isinstance(calibrate, dict):
+            raise TypeError(f"evaluate: calibrate must be None, one of {K.MODES} or a "
+                            f"calibration dict, got {type(calibrate).__name__}")
+        K.bin_edges(n_bins)
     modules = (image_encoder, text_encoder, fusion_model)
     flags = [(m, m.training) for top in modules for m in top.modules()]
     logits_buf = labels_buf = None
@@ -264,10 +331,34 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
             ym = torch.where(ign, torch.zeros_like(y), y)
             counts = F.auroc_counts(zm, ym)
             thr = torch.from_numpy(thr_host).to(z.device)
-            tp, fp = F.confusion_grid(zm, ym, thr)
+            extra = []
+            z_sweep = zm
+            if calibrate is not None:
+                if isinstance(calibrate, str):
+                    scale, bias, status, _ = F.calib_fit(z, y, mode=calibrate)
+                    cal_mode = calibrate
+                else:
+                    scale, bias = K.from_dict(calibrate, z.shape[1], z.device)
+                    status = torch.tensor([int(v) for v in calibrate.get(
+                        "status", [0] * z.shape[1])], dtype=torch.int32, device=z.device)
+                    cal_mode = calibrate["mode"]
+                z_cal = z * scale + bias  # a multiply and an add, as the kernels compute z'
+                z_sweep = torch.where(ign, torch.full_like(z, math.nan), z_cal)
+                bins0, nan0 = F.reliability_bins(zm, ym, n_bins=n_bins)
+                bins1, nan1 = F.reliability_bins(zm, ym, scale, bias, n_bins=n_bins)
+                # the plain NLL of the labelled elements: one evaluation pass at the identity
+                info0 = F.calib_fit(z, y, iters=0, smooth=False)[3]
+                info1 = F.calib_fit(z_cal, y, iters=0, smooth=False)[3]
+                extra = [bins0.reshape(-1), nan0, bins1.reshape(-1), nan1,
+                         scale.view(torch.int32).to(torch.int64),
+                         bias.view(torch.int32).to(torch.int64), status.to(torch.int64),
+                         info0[:, 0].contiguous().view(torch.int64),
+                         info1[:, 0].contiguous().view(torch.int64),
+                         info0[:, 3].contiguous().view(torch.int64)]
+            tp, fp = F.confusion_grid(z_sweep, ym, thr)
             packed = torch.cat([counts.reshape(-1), tp.reshape(-1), fp.reshape(-1),
-                                ignored.reshape(-1).to(torch.int64),
-                                loss.reshape(1).view(torch.int32).to(torch.int64)])
+                                ignored.reshape(-1).to(torch.int64)] + extra +
+                               [loss.reshape(1).view(torch.int32).to(torch.int64)])
             host = packed.cpu().numpy()  # the one device-to-host copy
     finally:
         for m, was in flags:
@@ -289,6 +380,9 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
            "val_f1_micro": picked["micro"]["f1"],
            "val_f1_micro_at_0p5": picked["micro_at_0p5"]["f1"],
            "per_class": picked["per_class"]}
+    if calibrate is not None:
+        out["calibration"] = _calibration_report(
+            host[(C + 1) * 4 + 2 * C * T + C:-1], C, n_bins, ign_h, cal_mode)
     if generate and has_head:
         width = max(g.shape[1] for g in gen_ids)
         pred = [row + [0] * (width - len(row)) for g in gen_ids for row in g.tolist()]

@@ -153,7 +153,7 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
-                   augment=None, criterion=None, uncertain=None):
+                   augment=None, criterion=None, uncertain=None, calibrate=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -176,7 +176,21 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     under artifacts["loss"]; without it the bundle is what it was.  uncertain (a
     data.apply_uncertain policy, default None) maps the -1 labels of the training batches and of
     the fusion rows; the validation loader then uses "ignore", so uncertain labels are left out
-    of the metrics.  NaN (missing) labels need a criterion: the plain loss returns NaN on them."""
+    of the metrics.  NaN (missing) labels need a criterion: the plain loss returns NaN on them.
+
+    calibrate ("temperature" or "platt", default None = the bundle is what it was) fits that
+    probability calibration on the held-out rows (evaluate(calibrate=...), so it needs
+    val_rows > 0: ValueError otherwise), stores the map under artifacts["calibration"], where
+    inference() finds it, and registers the in-sample val_ece_micro after calibration; the
+    stored thresholds then refer to the calibrated probabilities."""
+    if calibrate is not None:
+        from .calibration import MODES
+        if calibrate not in MODES:
+            raise ValueError(f"training_tests: calibrate must be None or one of {MODES}, got "
+                             f"{calibrate!r}")
+        if val_rows <= 0:
+            raise ValueError("training_tests(calibrate=...) fits on held-out rows: it needs "
+                             "val_rows > 0")
     from PIL import Image
     from . import training_pipeline as TP
     from .data import LocalCXRBatches, apply_uncertain
@@ -349,6 +363,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
 
     metrics = {"val_auroc_micro": 0.874, "val_rougeL": 0.214}  # TP:1112 placeholders
     thresholds = [0.5] * 13
+    calibration = None
     if val_df is not None:
         from .metrics import evaluate
         log("----------VALIDATION----------")
@@ -361,12 +376,19 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                                        shuffle=False, device=dev,
                                        uncertain=None if uncertain is None else "ignore"),
                        generate=True, gen_kwargs=gen, report_labels=val_labels,
-                       criterion=None if plain_loss else criterion)
+                       criterion=None if plain_loss else criterion, calibrate=calibrate)
         out["val"] = val
         metrics = {k: (None if v != v else v) for k, v in
                    ((k, val[k]) for k in ("val_auroc_micro", "val_auroc_macro", "val_loss",
                                           "val_f1_micro", "val_rougeL"))}
         thresholds = val["thresholds"]
+        if calibrate is not None:
+            cal = val["calibration"]
+            calibration = {k: cal[k] for k in ("mode", "scale", "bias", "status")}
+            ece = cal["after"]["val_ece_micro"]
+            metrics["val_ece_micro"] = None if ece != ece else ece
+            log(f"[VAL] calibration {calibrate}: ece micro {cal['before']['val_ece_micro']:.4f}"
+                f" -> {ece:.4f} (in-sample), status {cal['status']}")
         log(f"[VAL] n={val['n']} loss={val['val_loss']:.4f} auroc micro="
             f"{val['val_auroc_micro']:.4f} macro={val['val_auroc_macro']:.4f} f1 micro="
             f"{val['val_f1_micro']:.4f} (at 0.5: {val['val_f1_micro_at_0p5']:.4f}) rougeL="
@@ -376,6 +398,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         artifacts = {"class_names": list(DISEASES), "thresholds": thresholds}
         if not plain_loss:
             artifacts["loss"] = criterion.config()
+        if calibration is not None:
+            artifacts["calibration"] = calibration
         rm = save_model_to_hopsworks_model_registry(
             fusion_model=fusion_model, text_encoder=text_encoder, image_encoder=image_encoder,
             model_name=model_name, description="CXR fusion: CNN+Text -> MLP; multi-label "
