@@ -7,34 +7,22 @@
 // is iters + 1 such launches on one stream with no host sync between them; the state (trial
 // point, accepted point and its sums, lambda) lives in the workspace.
 //
-// Layout: that of disease_loss_fwd_kernel (loss.hip).  A block uses TB = (256 / C) * C threads;
-// thread t = blockIdx * TB + tid walks elements t, t + S, ... with S = gridDim * TB, so it stays
-// in class tid % C and the threads of a block form R = TB / C rows of C classes.  The element
-// terms are fp32 (one max-shifted expf, one log1pf); the sums are fp64 from the thread upward,
-// through a fixed-order LDS row tree, then per-block partials in the workspace, which the block
-// that draws the last ticket of an integer counter adds in block order.  No float atomics: the
-// result is a function of (N, C, data) alone, bit-reproducible.  The hand-off is the agent-scope
-// release / acquire pair around the ticket; partials are read with agent-scope atomic loads.
+// Layout and hand-off: the class-aligned reduction of class_reduce.h.  The element terms are
+// fp32 (one max-shifted expf, one log1pf); the sums are fp64 from the thread upward.  No float
+// atomics: the result is a function of (N, C, data) alone, bit-reproducible.
 //
 // reliability_bins_kernel counts, per class and probability bin, the elements, the positives and
 // the fixed-point sums of p and (p - y)^2: the upper-bound search over LDS-resident edges and
 // the per-block LDS histogram of confusion_grid_kernel (metrics.hip), integer atomics only.
 #include <math.h>
 
-#include "common.h"
+#include "class_reduce.h"
 #include "../../include/mmdx.h"
 
 namespace mmdx {
 
-typedef unsigned long long u64;
-
-constexpr int CAL_NT = 256;          // threads per block
-constexpr int CAL_MAX_C = 64;        // as the loss and the metrics kernels
-constexpr int CAL_PER_THREAD = 8;    // elements per thread before the grid grows
-constexpr int CAL_MAX_BLOCKS = 1024;
 constexpr int CAL_NSUM = 7;          // NLL, ga, gb, haa, hab, hbb, labelled count
 constexpr int CAL_STATE = 16;        // doubles of state per class
-constexpr size_t CAL_WS_HEAD = 16;   // the ticket counter, padded to 16 bytes
 constexpr double CAL_LAMBDA0 = 1e-3, CAL_LAMBDA_MIN = 1e-9, CAL_LAMBDA_MAX = 1e12;
 constexpr double CAL_SLACK = 1e-9;   // relative slack of the acceptance test
 constexpr long REL_MAX_ITEMS = 1L << 24;
@@ -45,44 +33,25 @@ constexpr int REL_CELLS = 1536;      // (class, bin) cells of 4 x u64 per block:
 enum { ST_A = 0, ST_B, ST_LAMBDA, ST_A_ACC, ST_B_ACC, ST_F_ACC, ST_GA, ST_GB, ST_HAA, ST_HAB,
        ST_HBB, ST_F0, ST_N };
 
-static inline int cal_tb(int C) { return (CAL_NT / C) * C; }
-static inline int cal_grid(long n, int C) {
-  const long per = (long)cal_tb(C) * CAL_PER_THREAD;
-  return (int)std::max<long>(1, std::min<long>((n + per - 1) / per, CAL_MAX_BLOCKS));
-}
-
-// red holds CAL_NSUM planes of R rows of C values; afterwards row 0 of each plane is the sum over
-// the rows, added pairwise in a fixed order.  Every thread of the block calls it.
-__device__ __forceinline__ void rows_tree7(double* red, int tid, int C, int R) {
-  int s = 1;
-  while (s < R) s <<= 1;
-  for (s >>= 1; s >= 1; s >>= 1) {
-    if (tid < s * C && tid + s * C < R * C) {
-#pragma unroll
-      for (int k = 0; k < CAL_NSUM; ++k) red[k * CAL_NT + tid] += red[k * CAL_NT + tid + s * C];
-    }
-    __syncthreads();
-  }
-}
-
 __device__ __forceinline__ bool finite_d(double x) { return fabs(x) < INFINITY; }
 
-__global__ __launch_bounds__(CAL_NT) void calib_fit_kernel(
+__global__ __launch_bounds__(CLS_NT) void calib_fit_kernel(
     const float* __restrict__ z, const float* __restrict__ y, long n, int C,
     const double* __restrict__ counts, int smooth, int temperature, int first, int last,
     double min_count, double tol, float* __restrict__ scale, float* __restrict__ bias,
     int* __restrict__ status, double* __restrict__ info, unsigned* counter, double* state,
     u64* part) {
-  __shared__ double red[CAL_NSUM * CAL_NT];
-  __shared__ unsigned ticket_s;
+  __shared__ double red[CAL_NSUM * CLS_NT];  // CAL_NSUM planes of R rows of C values
   const int tid = threadIdx.x;
-  const int TB = (CAL_NT / C) * C, R = TB / C;
+  const int TB = cls_tb(C), R = TB / C;
+  const auto add = [&](int dst, int src) {
+#pragma unroll
+    for (int k = 0; k < CAL_NSUM; ++k) red[k * CLS_NT + dst] += red[k * CLS_NT + src];
+  };
   const int c = tid % C;
   const long S = (long)gridDim.x * TB;
 
-  double acc[CAL_NSUM];
-#pragma unroll
-  for (int k = 0; k < CAL_NSUM; ++k) acc[k] = 0.0;
+  double acc[CAL_NSUM] = {};
   if (tid < TB) {
     // the trial point, as fp32: the first pass starts at the identity whatever the state holds
     const float a = first ? 1.f : (float)state[c * CAL_STATE + ST_A];
@@ -98,12 +67,10 @@ __global__ __launch_bounds__(CAL_NT) void calib_fit_kernel(
       if (yi == yi) {  // a NaN target is "no label"
         const float u = __fadd_rn(__fmul_rn(a, zi), b);  // never contracted: z' as the host has it
         const float tt = t_neg + yi * t_dif;
-        // e = exp(-|u|) in [0, 1]: sigmoid and softplus of either sign without overflow
-        const float e = expf(-fabsf(u));
+        float pf, qf, e;  // sigmoid(u), sigmoid(-u), exp(-|u|)
+        sigmoid_parts(u, &pf, &qf, &e);
         const float l1p = log1pf(e);
-        const float hi = 1.f / (1.f + e), lo = e / (1.f + e);
-        const double p = u >= 0.f ? hi : lo, q = u >= 0.f ? lo : hi;  // sigmoid(u), sigmoid(-u)
-        const double ud = u, zd = zi, td = tt;
+        const double p = pf, q = qf, ud = u, zd = zi, td = tt;
         const double d = p - td, w = p * q;
         acc[0] += fmax(ud, 0.0) + (double)l1p - td * ud;
         acc[1] += d * zd;
@@ -116,52 +83,30 @@ __global__ __launch_bounds__(CAL_NT) void calib_fit_kernel(
     }
   }
 #pragma unroll
-  for (int k = 0; k < CAL_NSUM; ++k) red[k * CAL_NT + tid] = acc[k];
+  for (int k = 0; k < CAL_NSUM; ++k) red[k * CLS_NT + tid] = acc[k];
   __syncthreads();
-  rows_tree7(red, tid, C, R);
+  rows_tree(tid, C, R, add);
 
   if (gridDim.x > 1) {
     if (tid < C) {
 #pragma unroll
       for (int k = 0; k < CAL_NSUM; ++k)
-        __hip_atomic_store(part + ((long)blockIdx.x * CAL_NSUM + k) * C + tid,
-                           (u64)__double_as_longlong(red[k * CAL_NT + tid]), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        cls_part_store(part + ((long)blockIdx.x * CAL_NSUM + k) * C + tid, red[k * CLS_NT + tid]);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned ticket =
-          __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ticket == gridDim.x - 1) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      ticket_s = ticket;
-    }
-    __syncthreads();
-    if (ticket_s != gridDim.x - 1) return;
-    // the last block: every block's partials are visible; add them in block order.  Thread tid
-    // takes the blocks tid / C, tid / C + R, ... of class tid % C, then the same row tree.
+    if (!cls_last_block(counter)) return;
 #pragma unroll
     for (int k = 0; k < CAL_NSUM; ++k) acc[k] = 0.0;
-    if (tid < TB) {
-      for (int blk = tid / C; blk < (int)gridDim.x; blk += R) {
+    cls_gather(tid, C, R, gridDim.x, [&](int blk, int cls) {
 #pragma unroll
-        for (int k = 0; k < CAL_NSUM; ++k)
-          acc[k] += __longlong_as_double((long long)__hip_atomic_load(
-              part + ((long)blk * CAL_NSUM + k) * C + c, __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT));
-      }
-    }
+      for (int k = 0; k < CAL_NSUM; ++k)
+        acc[k] += cls_part_f64(part + ((long)blk * CAL_NSUM + k) * C + cls);
+    });
 #pragma unroll
-    for (int k = 0; k < CAL_NSUM; ++k) red[k * CAL_NT + tid] = acc[k];
+    for (int k = 0; k < CAL_NSUM; ++k) red[k * CLS_NT + tid] = acc[k];
     __syncthreads();
-    rows_tree7(red, tid, C, R);
+    rows_tree(tid, C, R, add);
     // every block has drawn its ticket: the counter is ready for the next launch on the stream
-    if (tid == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) cls_part_store(counter, 0u);
   }
 
   if (tid >= C) return;
@@ -173,13 +118,13 @@ __global__ __launch_bounds__(CAL_NT) void calib_fit_kernel(
     n_pos = n_neg = 0.0;
     for (int j = 0; j < C; ++j) {  // class order
 #pragma unroll
-      for (int k = 0; k < CAL_NSUM; ++k) s[k] += red[k * CAL_NT + j];
+      for (int k = 0; k < CAL_NSUM; ++k) s[k] += red[k * CLS_NT + j];
       n_pos += counts[2 * j];
       n_neg += counts[2 * j + 1];
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < CAL_NSUM; ++k) s[k] = red[k * CAL_NT + tid];
+    for (int k = 0; k < CAL_NSUM; ++k) s[k] = red[k * CLS_NT + tid];
     n_pos = counts[2 * tid];
     n_neg = counts[2 * tid + 1];
   }
@@ -247,24 +192,24 @@ __global__ __launch_bounds__(CAL_NT) void calib_fit_kernel(
 // sigmoid(-z'), both rounded to multiples of 2^-30.  A block covers the classes
 // [blockIdx.y * CC, + CC) so that the histogram fits LDS for every legal (C, n_bins); the micro
 // row is the sum of the block's class rows, so the element loop has no single hot cell.
-__global__ __launch_bounds__(CAL_NT) void reliability_bins_kernel(
+__global__ __launch_bounds__(CLS_NT) void reliability_bins_kernel(
     const float* __restrict__ logits, const float* __restrict__ target, int N, int C,
     const float* __restrict__ scale, const float* __restrict__ bias,
     const float* __restrict__ edges, int n_bins, int CC, u64* __restrict__ out) {
   __shared__ u64 hist[REL_CELLS * 4];           // [cc][n_bins][4]
-  __shared__ unsigned nanc[CAL_MAX_C];
+  __shared__ unsigned nanc[CLS_MAX_C];
   __shared__ float sedge[REL_MAX_BINS];
   const int t = threadIdx.x;
   const int c0 = blockIdx.y * CC;
   const int cc = min(CC, C - c0);
   const int T = n_bins - 1;
-  for (int q = t; q < T; q += CAL_NT) sedge[q] = edges[q];
-  for (int q = t; q < cc * n_bins * 4; q += CAL_NT) hist[q] = 0;
-  for (int q = t; q < cc; q += CAL_NT) nanc[q] = 0;
+  for (int q = t; q < T; q += CLS_NT) sedge[q] = edges[q];
+  for (int q = t; q < cc * n_bins * 4; q += CLS_NT) hist[q] = 0;
+  for (int q = t; q < cc; q += CLS_NT) nanc[q] = 0;
   __syncthreads();
 
   const int M = N * C;
-  for (int e = blockIdx.x * CAL_NT + t; e < M; e += gridDim.x * CAL_NT) {
+  for (int e = blockIdx.x * CLS_NT + t; e < M; e += gridDim.x * CLS_NT) {
     const int cg = e % C, cl = cg - c0;
     if ((unsigned)cl >= (unsigned)cc) continue;
     float x = logits[e];
@@ -274,14 +219,9 @@ __global__ __launch_bounds__(CAL_NT) void reliability_bins_kernel(
       continue;
     }
     const bool pos = target[e] > 0.5f;
-    int lo = 0, hi = T;  // upper bound: first k with edges[k] > x
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sedge[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    const float ex = expf(-fabsf(x));
-    const float big = 1.f / (1.f + ex), small = ex / (1.f + ex);
-    const float p = x >= 0.f ? big : small, q = x >= 0.f ? small : big;
+    const int lo = upper_bound_lds(sedge, T, x);
+    float p, q, ex;
+    sigmoid_parts(x, &p, &q, &ex);
     const float d = pos ? q : p;  // |p - y|
     u64* h = hist + (cl * n_bins + lo) * 4;  // lo <= n_bins - 1
     atomicAdd(h + 0, (u64)1);
@@ -291,17 +231,17 @@ __global__ __launch_bounds__(CAL_NT) void reliability_bins_kernel(
   }
   __syncthreads();
   const int cells = n_bins * 4;
-  for (int q = t; q < cc * cells; q += CAL_NT) {
+  for (int q = t; q < cc * cells; q += CLS_NT) {
     const u64 v = hist[q];
     if (v) atomicAdd(out + (long)c0 * cells + q, v);
   }
-  for (int q = t; q < cells; q += CAL_NT) {  // micro: the block's classes, in class order
+  for (int q = t; q < cells; q += CLS_NT) {  // micro: the block's classes, in class order
     u64 v = 0;
     for (int j = 0; j < cc; ++j) v += hist[j * cells + q];
     if (v) atomicAdd(out + (long)C * cells + q, v);
   }
   u64* out_nan = out + (long)(C + 1) * cells;
-  for (int q = t; q < cc; q += CAL_NT)
+  for (int q = t; q < cc; q += CLS_NT)
     if (nanc[q]) atomicAdd(out_nan + c0 + q, (u64)nanc[q]);
   if (t == 0) {
     u64 v = 0;
@@ -310,19 +250,14 @@ __global__ __launch_bounds__(CAL_NT) void reliability_bins_kernel(
   }
 }
 
-static inline bool cal_overlaps(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
-
 }  // namespace mmdx
 
 using namespace mmdx;
 
 extern "C" size_t mmdx_calib_fit_workspace_size(long N, int C) {
-  if (N <= 0 || C <= 0 || C > CAL_MAX_C || N > (long)INT32_MAX / C) return 0;
-  return CAL_WS_HEAD + (size_t)C * CAL_STATE * sizeof(double) +
-         (size_t)cal_grid(N * C, C) * CAL_NSUM * C * sizeof(double);
+  if (N <= 0 || C <= 0 || C > CLS_MAX_C || N > (long)INT32_MAX / C) return 0;
+  return CLS_WS_HEAD + (size_t)C * CAL_STATE * sizeof(double) +
+         (size_t)cls_grid(N * C, C) * CAL_NSUM * C * sizeof(double);
 }
 
 extern "C" int mmdx_calib_fit_step(const float* logits, const float* target, long N, int C,
@@ -332,7 +267,7 @@ extern "C" int mmdx_calib_fit_step(const float* logits, const float* target, lon
                                    void* stream) {
   MMDX_CHECK_ARG(logits && target && counts, "calib_fit_step: null pointer");
   MMDX_CHECK_ARG(N > 0 && C > 0, "calib_fit_step: empty (N = %ld, C = %d)", N, C);
-  MMDX_CHECK_ARG(C <= CAL_MAX_C, "calib_fit_step: C = %d > %d", C, CAL_MAX_C);
+  MMDX_CHECK_ARG(C <= CLS_MAX_C, "calib_fit_step: C = %d > %d", C, CLS_MAX_C);
   MMDX_CHECK_ARG(N <= (long)INT32_MAX / C, "calib_fit_step: N * C exceeds 2^31 - 1 (N = %ld)", N);
   MMDX_CHECK_ARG(mode == MMDX_CALIB_TEMPERATURE || mode == MMDX_CALIB_PLATT,
                  "calib_fit_step: mode %d", mode);
@@ -352,24 +287,19 @@ extern "C" int mmdx_calib_fit_step(const float* logits, const float* target, lon
   const size_t outs_n[5] = {cb, cb, cb, (size_t)C * 32, need};
   const void* ins[3] = {logits, target, counts};
   const size_t ins_n[3] = {fb, fb, (size_t)C * 16};
-  for (int a = 0; a < 5; ++a) {
-    for (int b = 0; b < 3; ++b)
-      MMDX_CHECK_ARG(!cal_overlaps(outs[a], outs_n[a], ins[b], ins_n[b]),
-                     "calib_fit_step: an output overlaps an input");
-    for (int b = a + 1; b < 5; ++b)
-      MMDX_CHECK_ARG(!cal_overlaps(outs[a], outs_n[a], outs[b], outs_n[b]),
-                     "calib_fit_step: two outputs overlap");
-  }
+  const int clash = ranges_clash(outs, outs_n, 5, ins, ins_n, 3);
+  MMDX_CHECK_ARG(clash != CLASH_INPUT, "calib_fit_step: an output overlaps an input");
+  MMDX_CHECK_ARG(clash != CLASH_OUTPUT, "calib_fit_step: two outputs overlap");
   hipStream_t st = (hipStream_t)stream;
-  const int grid = cal_grid(n, C);
+  const int grid = cls_grid(n, C);
   unsigned* counter = (unsigned*)workspace;
-  double* state = (double*)((char*)workspace + CAL_WS_HEAD);
+  double* state = (double*)((char*)workspace + CLS_WS_HEAD);
   u64* part = (u64*)(state + (size_t)C * CAL_STATE);
   if (pass == 0 && grid > 1) {  // later passes find the counter reset by the last block
-    const hipError_t e = hipMemsetAsync(workspace, 0, CAL_WS_HEAD, st);
+    const hipError_t e = hipMemsetAsync(workspace, 0, CLS_WS_HEAD, st);
     MMDX_CHECK_ARG(e == hipSuccess, "calib_fit_step: hipMemsetAsync: %s", hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(calib_fit_kernel, dim3(grid), dim3(CAL_NT), 0, st, logits, target, n, C,
+  hipLaunchKernelGGL(calib_fit_kernel, dim3(grid), dim3(CLS_NT), 0, st, logits, target, n, C,
                      counts, smooth != 0, mode == MMDX_CALIB_TEMPERATURE, pass == 0, last != 0,
                      (double)min_count, tol, scale, bias, status, info, counter, state, part);
   MMDX_LAUNCH_CHECK();
@@ -381,7 +311,7 @@ extern "C" int mmdx_reliability_bins(const float* logits, const float* target, i
                                      int n_bins, int64_t* out, void* stream) {
   MMDX_CHECK_ARG(logits && target && out, "reliability_bins: null pointer");
   MMDX_CHECK_ARG(N > 0 && C > 0, "reliability_bins: empty (N = %d, C = %d)", N, C);
-  MMDX_CHECK_ARG(C <= CAL_MAX_C, "reliability_bins: C = %d > %d", C, CAL_MAX_C);
+  MMDX_CHECK_ARG(C <= CLS_MAX_C, "reliability_bins: C = %d > %d", C, CLS_MAX_C);
   MMDX_CHECK_ARG((long)N * C <= REL_MAX_ITEMS,
                  "reliability_bins: N * C = %ld exceeds the limit 2^24", (long)N * C);
   MMDX_CHECK_ARG(n_bins >= 1 && n_bins <= REL_MAX_BINS,
@@ -396,7 +326,7 @@ extern "C" int mmdx_reliability_bins(const float* logits, const float* target, i
   const int CC = std::min(C, REL_CELLS / n_bins);  // >= 24 classes per block
   const int M = N * C;
   const int gx = std::max(1, std::min((M + 4095) / 4096, 256));
-  hipLaunchKernelGGL(reliability_bins_kernel, dim3(gx, (C + CC - 1) / CC), dim3(CAL_NT), 0, st,
+  hipLaunchKernelGGL(reliability_bins_kernel, dim3(gx, (C + CC - 1) / CC), dim3(CLS_NT), 0, st,
                      logits, target, N, C, scale, bias, edges, n_bins, CC, (u64*)out);
   MMDX_LAUNCH_CHECK();
   return 0;

@@ -7,15 +7,12 @@
 // CPU reference can be matched exactly.  No float atomics, no sort, no workspace.
 #include <math.h>
 
-#include "common.h"
+#include "class_reduce.h"  // u64, CLS_MAX_C, upper_bound_lds
 #include "../../include/mmdx.h"
 
 namespace mmdx {
 
-typedef unsigned long long u64;
-
 constexpr int MET_NT = 256;
-constexpr int MET_MAX_C = 64;
 constexpr long MET_MAX_ITEMS = 1L << 24;  // N * C
 constexpr int AUROC_TILE = 4096;          // j items (floats) staged per pass: 16 KiB
 constexpr int AUROC_CHUNK = 1024;         // i items per block (its positives: 256 per round)
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(MET_NT) void auroc_pairs_kernel(const float* __rest
   __shared__ __attribute__((aligned(16))) float tile[AUROC_TILE];
   __shared__ float pos_s[AUROC_CHUNK];
   __shared__ unsigned char pos_c[AUROC_CHUNK];
-  __shared__ u64 acc[(MET_MAX_C + 1) * 4];
+  __shared__ u64 acc[(CLS_MAX_C + 1) * 4];
   __shared__ int n_list;
   const int t = threadIdx.x;
   const int M = N * C;
@@ -165,11 +162,7 @@ __global__ __launch_bounds__(MET_NT) void confusion_grid_kernel(
     if ((unsigned)cl >= (unsigned)cc) continue;
     const float x = logits[e];
     const int neg = target[e] > 0.5f ? 0 : 1;
-    int lo = 0, hi = T;  // upper bound: first t with thr[t] > x
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sthr[mid] <= x) lo = mid + 1; else hi = mid;
-    }
+    const int lo = upper_bound_lds(sthr, T, x);
     if (lo) atomicAdd(&hist[(neg * cc + cl) * T1 + lo], 1u);  // lo <= T
   }
   __syncthreads();
@@ -202,7 +195,7 @@ extern "C" int mmdx_auroc_pairs(const float* scores, const float* target, int N,
                                 int64_t* out, void* stream) {
   MMDX_CHECK_ARG(scores && target && out, "auroc_pairs: null pointer");
   MMDX_CHECK_ARG(N > 0 && C > 0, "auroc_pairs: empty (N = %d, C = %d)", N, C);
-  MMDX_CHECK_ARG(C <= MET_MAX_C, "auroc_pairs: C = %d > %d", C, MET_MAX_C);
+  MMDX_CHECK_ARG(C <= CLS_MAX_C, "auroc_pairs: C = %d > %d", C, CLS_MAX_C);
   MMDX_CHECK_ARG((long)N * C <= MET_MAX_ITEMS,
                  "auroc_pairs: N * C = %ld exceeds the all-pairs limit 2^24", (long)N * C);
   hipStream_t st = (hipStream_t)stream;
@@ -224,7 +217,7 @@ extern "C" int mmdx_confusion_grid(const float* logits, const float* target, int
                                    void* stream) {
   MMDX_CHECK_ARG(logits && target && thr && tp && fp, "confusion_grid: null pointer");
   MMDX_CHECK_ARG(N > 0 && C > 0, "confusion_grid: empty (N = %d, C = %d)", N, C);
-  MMDX_CHECK_ARG(C <= MET_MAX_C, "confusion_grid: C = %d > %d", C, MET_MAX_C);
+  MMDX_CHECK_ARG(C <= CLS_MAX_C, "confusion_grid: C = %d > %d", C, CLS_MAX_C);
   MMDX_CHECK_ARG((long)N * C <= MET_MAX_ITEMS,
                  "confusion_grid: N * C = %ld exceeds the limit 2^24", (long)N * C);
   MMDX_CHECK_ARG(T >= 1 && T <= GRID_MAX_T, "confusion_grid: T = %d outside [1, %d]", T,
