@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "dropout_rng.h"
 #include "igemm.h"
 #include "../../include/mmdx.h"
 #include <mutex>
@@ -48,10 +49,14 @@ constexpr int HD = 64;           // head dim
 constexpr int MAXKT = 16;        // max 16-key tiles (L <= 256)
 constexpr float MASK_NEG = -1e30f;
 
-template <typename T> struct AttnCfg;
-template <> struct AttnCfg<bf16> { static constexpr int NW = 4; };   // 64 query rows / block
-template <> struct AttnCfg<float> { static constexpr int NW = 2; };  // 32 query rows / block
-template <> struct AttnCfg<f16> { static constexpr int NW = 4; };
+constexpr int NW32 = 2;          // waves of an fp32 block: 32 query (key) rows
+
+// L rounded up to the 16-bit MFMA K (32): the padded key / query extent of every LDS image
+__host__ __device__ constexpr int attn_lp(int L) { return (L + 31) & ~31; }
+// blocks of 16 * nw rows per (batch, head)
+__host__ __device__ constexpr int blocks_per_head(int L, int nw) {
+  return (L + nw * 16 - 1) / (nw * 16);
+}
 
 __device__ __forceinline__ float rowgroup_max(float v) {
 #pragma unroll
@@ -150,48 +155,68 @@ __device__ __forceinline__ void attn_block(int nb, int H, int& blk, int& h, int&
   b = hl / H;
 }
 
-__device__ __forceinline__ uint32_t attn_hash64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return (uint32_t)x;
+// additive key mask as BertSelfAttention: large negative on pads, -inf beyond L
+__device__ __forceinline__ float key_mask_add(const int64_t* mask, int b, int L, int key) {
+  return key < L ? (mask && mask[(long)b * L + key] == 0 ? MASK_NEG : 0.f) : -INFINITY;
 }
+
+// Dropout on the probabilities of one (batch, head): element (q, key) of the head is element
+// ((b*H + h)*L + q)*L + key of the launch's stream (dropout_rng.h), i.e. element q*L + key
+// past head_stream().
+__device__ __forceinline__ uint64_t head_stream(uint64_t stream, int b, int h, int H, int L) {
+  return stream + (((uint64_t)b * H + h) * L) * (uint64_t)L;
+}
+// The flash-style backward kernels' redraw of the forward's keep bits.  `stream` is the
+// launch's stream base; it is not looked at when p == 0.  (The forward kernels keep these as
+// plain locals: the struct moved their instruction schedule and cost the dropout forward
+// 0.2 us at the BERT shape.)
+struct HeadDropout {
+  float p, keep_scale;   // keep_scale = 1 / (1 - p)
+  uint64_t base;         // stream base + the head's first element
+  int L;
+  __device__ __forceinline__ HeadDropout(float p_drop, uint64_t stream, int b, int h, int H,
+                                         int L_)
+      : p(p_drop), keep_scale(p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f),
+        base(p_drop > 0.f ? head_stream(stream, b, h, H, L_) : 0ull), L(L_) {}
+  __device__ __forceinline__ bool keep(int q, int key) const {
+    return !(p > 0.f) || dropout_keep(base, (uint64_t)q * L + key, p);
+  }
+};
 
 // (launch bounds: the LDS footprint allows two blocks per CU; the default 1024-thread budget
 // of 128 VGPRs spilled the staged K / V vectors)
-template <typename T>
-__global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
-    const T* __restrict__ qkv, const int64_t* __restrict__ mask, const float* __restrict__ bias,
+__global__ __launch_bounds__(NW32 * 64, 2) void attn_fwd_kernel(
+    const float* __restrict__ qkv, const int64_t* __restrict__ mask, const float* __restrict__ bias,
     int causal, int L, int H, float scale, float p_drop, uint64_t seed,
-    const uint64_t* __restrict__ ctr, T* __restrict__ out, float* __restrict__ probs) {
-  typedef MfmaOp<T> Op;
-  constexpr int NW = AttnCfg<T>::NW, QB = NW * 16, PAD = Vec16<T>::N;
+    const uint64_t* __restrict__ ctr, float* __restrict__ out, float* __restrict__ probs) {
+  typedef MfmaOp<float> Op;
+  constexpr int NW = NW32, QB = NW * 16, PAD = Vec16<float>::N;
   constexpr int LDQ = HD + PAD;
-  const int LP = (L + 31) & ~31;  // multiple of the bf16 MFMA K (32)
+  const int LP = attn_lp(L);
   const int LDV = LP + PAD;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int KP = max(LP * LDQ, QB * LDV);
-  T* Ks = (T*)smem_raw;                 // [LP][LDQ]; P [QB][LDV] reuses it after S = QK^T
-  T* Ps = Ks;
-  T* Vt = Ks + KP;                      // [HD][LDV]
-  T* Qs = Vt + HD * LDV;                // [QB][LDQ]
+  float* Ks = (float*)smem_raw;         // [LP][LDQ]; P [QB][LDV] reuses it after S = QK^T
+  float* Ps = Ks;
+  float* Vt = Ks + KP;                  // [HD][LDV]
+  float* Qs = Vt + HD * LDV;            // [QB][LDQ]
   const int q0 = blockIdx.x * QB, h = blockIdx.y, b = blockIdx.z;
   const int nth = NW * 64;
   const long row_ld = 3L * H * HD;
-  const T* base = qkv + (long)b * L * row_ld + h * HD;
-  stage_pair<T, 4, false, true>(Ks, LDQ, base + (long)H * HD, Vt, LDV, base + 2L * H * HD,
-                                row_ld, LP, L, nth);
-  stage_rows<T, 4, false>(Qs, LDQ, base + (long)q0 * row_ld, row_ld, QB, min(QB, L - q0), nth);
+  const float* base = qkv + (long)b * L * row_ld + h * HD;
+  stage_pair<float, 4, false, true>(Ks, LDQ, base + (long)H * HD, Vt, LDV, base + 2L * H * HD,
+                                    row_ld, LP, L, nth);
+  stage_rows<float, 4, false>(Qs, LDQ, base + (long)q0 * row_ld, row_ld, QB, min(QB, L - q0), nth);
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nkt = LP / 16;
   f32x4 s[MAXKT];
-  const T* a_s = Qs + (wid * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
+  const float* a_s = Qs + (wid * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
 #pragma unroll
   for (int j = 0; j < MAXKT; ++j) {
     s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (j < nkt) {
-      const T* b_s = Ks + (j * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
+      const float* b_s = Ks + (j * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
 #pragma unroll
       for (int k = 0; k < HD; k += Op::KS) s[j] = Op::mma(Op::ld(a_s + k), Op::ld(b_s + k), s[j]);
     }
@@ -202,7 +227,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
   for (int j = 0; j < MAXKT; ++j) {
     if (j >= nkt) continue;
     const int key = j * 16 + (lane & 15);
-    const float madd = key < L ? (mask && mask[(long)b * L + key] == 0 ? MASK_NEG : 0.f) : -INFINITY;
+    const float madd = key_mask_add(mask, b, L, key);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = q0 + wid * 16 + (lane >> 4) * 4 + r;
@@ -232,9 +257,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
   float* prow = probs ? probs + (((long)b * H + h) * L) * L : nullptr;
   const bool drop = p_drop > 0.f;
   const float keep_scale = drop ? 1.f / (1.f - p_drop) : 1.f;
-  const uint64_t rbase = drop ? seed * 0x9E3779B97F4A7C15ULL + (ctr ? ctr[0] << 32 : 0ull) +
-                                    (((uint64_t)b * H + h) * L) * (uint64_t)L
-                              : 0ull;
+  const uint64_t rbase = drop ? head_stream(dropout_stream_base(seed, ctr), b, h, H, L) : 0ull;
 #pragma unroll
   for (int j = 0; j < MAXKT; ++j) {
     if (j >= nkt) continue;
@@ -245,11 +268,8 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
       const float p = s[j][r] * sum[r];
       const int q = q0 + rl;
       bool keep = true;
-      if (drop) {
-        const float u = (attn_hash64(rbase + (uint64_t)q * L + key) >> 8) * (1.f / 16777216.f);
-        keep = u >= p_drop;
-      }
-      Ps[rl * LDV + key] = from_f<T>(keep ? p * keep_scale : 0.f);
+      if (drop) keep = dropout_keep(rbase, (uint64_t)q * L + key, p_drop);
+      Ps[rl * LDV + key] = keep ? p * keep_scale : 0.f;
       if (prow && q < L && key < L) prow[(long)q * L + key] = keep ? p : -p;
     }
   }
@@ -258,12 +278,12 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
   f32x4 o[HD / 16];
 #pragma unroll
   for (int j = 0; j < HD / 16; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const T* p_s = Ps + (wid * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
+  const float* p_s = Ps + (wid * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
   for (int k = 0; k < LP; k += Op::KS) {
     const typename Op::frag_t af = Op::ld(p_s + k);
 #pragma unroll
     for (int j = 0; j < HD / 16; ++j) {
-      const T* v_s = Vt + (j * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
+      const float* v_s = Vt + (j * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
       o[j] = Op::mma(af, Op::ld(v_s + k), o[j]);
     }
   }
@@ -272,49 +292,47 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = q0 + wid * 16 + (lane >> 4) * 4 + r;
-      if (q < L) out[(((long)b * L + q) * H + h) * HD + j * 16 + (lane & 15)] = from_f<T>(o[j][r]);
+      if (q < L) out[(((long)b * L + q) * H + h) * HD + j * 16 + (lane & 15)] = o[j][r];
     }
 }
 
-// Backward A: per query block -> dS (T, global scratch [B,H,L,LP]) and dQ.
-template <typename T>
+// Backward A: per query block -> dS (global scratch [B,H,L,LP]) and dQ.
 // (launch bounds: without them the compiler budgets registers for 1024-thread blocks, 128
 // VGPRs, and spilled 17 of the dP row tiles to scratch; the LDS footprint allows two blocks
 // per CU = two waves per SIMD anyway)
-__global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_q_kernel(
-    const T* __restrict__ qkv, const float* __restrict__ probs,
-                                  const T* __restrict__ dout, int L, int H, float scale,
-                                  float keep_scale, T* __restrict__ dS_g,
-                                  T* __restrict__ dqkv) {
-  typedef MfmaOp<T> Op;
-  constexpr int NW = AttnCfg<T>::NW, QB = NW * 16, PAD = Vec16<T>::N;
+__global__ __launch_bounds__(NW32 * 64, 2) void attn_bwd_q_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ probs,
+    const float* __restrict__ dout, int L, int H, float scale, float keep_scale,
+    float* __restrict__ dS_g, float* __restrict__ dqkv) {
+  typedef MfmaOp<float> Op;
+  constexpr int NW = NW32, QB = NW * 16, PAD = Vec16<float>::N;
   constexpr int LDQ = HD + PAD;
-  const int LP = (L + 31) & ~31;  // multiple of the bf16 MFMA K (32)
+  const int LP = attn_lp(L);
   const int LDV = LP + PAD;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int KP = max(LP * LDQ, QB * LDV);
-  T* Vs = (T*)smem_raw;                 // [LP][LDQ] V rows (K-major for dP); dS reuses it
-  T* dSs = Vs;                          // [QB][LDV]
-  T* Kt = Vs + KP;                      // [HD][LDV]   K^T (for dQ)
-  T* dOs = Kt + HD * LDV;               // [QB][LDQ]
+  float* Vs = (float*)smem_raw;         // [LP][LDQ] V rows (K-major for dP); dS reuses it
+  float* dSs = Vs;                      // [QB][LDV]
+  float* Kt = Vs + KP;                  // [HD][LDV]   K^T (for dQ)
+  float* dOs = Kt + HD * LDV;           // [QB][LDQ]
   const int q0 = blockIdx.x * QB, h = blockIdx.y, b = blockIdx.z;
   const int nth = NW * 64;
   const long row_ld = 3L * H * HD;
-  const T* base = qkv + (long)b * L * row_ld + h * HD;
-  stage_pair<T, 8, false, true>(Vs, LDQ, base + 2L * H * HD, Kt, LDV, base + (long)H * HD,
-                                row_ld, LP, L, nth);
-  stage_rows<T, 4, false>(dOs, LDQ, dout + ((long)b * L + q0) * H * HD + h * HD, (long)H * HD,
-                          QB, min(QB, L - q0), nth);
+  const float* base = qkv + (long)b * L * row_ld + h * HD;
+  stage_pair<float, 8, false, true>(Vs, LDQ, base + 2L * H * HD, Kt, LDV, base + (long)H * HD,
+                                    row_ld, LP, L, nth);
+  stage_rows<float, 4, false>(dOs, LDQ, dout + ((long)b * L + q0) * H * HD + h * HD, (long)H * HD,
+                              QB, min(QB, L - q0), nth);
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nkt = LP / 16;
   f32x4 s[MAXKT];
-  const T* a_s = dOs + (wid * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
+  const float* a_s = dOs + (wid * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
 #pragma unroll
   for (int j = 0; j < MAXKT; ++j) {
     s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (j < nkt) {
-      const T* b_s = Vs + (j * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
+      const float* b_s = Vs + (j * 16 + (lane & 15)) * LDQ + (lane >> 4) * Op::FRAG;
 #pragma unroll
       for (int k = 0; k < HD; k += Op::KS) s[j] = Op::mma(Op::ld(a_s + k), Op::ld(b_s + k), s[j]);
     }
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_q_kernel(
 #pragma unroll
   for (int r = 0; r < 4; ++r) dot[r] = rowgroup_sum(dot[r]);
   __syncthreads();  // every wave is done reading V: dS may overwrite it
-  T* dsg = dS_g + (((long)b * H + h) * L) * LP;
+  float* dsg = dS_g + (((long)b * H + h) * L) * LP;
 #pragma unroll
   for (int j = 0; j < MAXKT; ++j) {
     if (j >= nkt) continue;
@@ -348,7 +366,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_q_kernel(
     for (int r = 0; r < 4; ++r) {
       const int rl = wid * 16 + (lane >> 4) * 4 + r;
       const float ds = pv[j][r] * (s[j][r] - dot[r]);
-      const T dst = from_f<T>(ds);
+      const float dst = ds;
       dSs[rl * LDV + key] = dst;
       const int q = q0 + rl;
       if (q < L) dsg[(long)q * LP + key] = dst;
@@ -358,12 +376,12 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_q_kernel(
   f32x4 o[HD / 16];
 #pragma unroll
   for (int j = 0; j < HD / 16; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const T* p_s = dSs + (wid * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
+  const float* p_s = dSs + (wid * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
   for (int k = 0; k < LP; k += Op::KS) {
     const typename Op::frag_t af = Op::ld(p_s + k);
 #pragma unroll
     for (int j = 0; j < HD / 16; ++j) {
-      const T* k_s = Kt + (j * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
+      const float* k_s = Kt + (j * 16 + (lane & 15)) * LDV + (lane >> 4) * Op::FRAG;
       o[j] = Op::mma(af, Op::ld(k_s + k), o[j]);
     }
   }
@@ -373,33 +391,32 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_q_kernel(
     for (int r = 0; r < 4; ++r) {
       const int q = q0 + wid * 16 + (lane >> 4) * 4 + r;
       if (q < L)
-        dqkv[((long)b * L + q) * 3 * H * HD + h * HD + j * 16 + (lane & 15)] =
-            from_f<T>(o[j][r] * scale);
+        dqkv[((long)b * L + q) * 3 * H * HD + h * HD + j * 16 + (lane & 15)] = o[j][r] * scale;
     }
 }
 
 // Backward B: per key block (16*NW keys): dV = P^T dO, dK = scale * dS^T Q, streaming
 // 32-query chunks through LDS.
 constexpr int QC = 32;
-template <typename T>
-__global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(const T* __restrict__ qkv, const float* __restrict__ probs,
-                                   const T* __restrict__ dout, const T* __restrict__ dS_g, int L,
-                                   int H, float scale, float keep_scale, T* __restrict__ dqkv) {
-  typedef MfmaOp<T> Op;
-  constexpr int NW = AttnCfg<T>::NW, KB = NW * 16, PAD = Vec16<T>::N;
+__global__ __launch_bounds__(NW32 * 64, 2) void attn_bwd_kv_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ probs,
+    const float* __restrict__ dout, const float* __restrict__ dS_g, int L, int H, float scale,
+    float keep_scale, float* __restrict__ dqkv) {
+  typedef MfmaOp<float> Op;
+  constexpr int NW = NW32, KB = NW * 16, PAD = Vec16<float>::N;
   constexpr int LDC = QC + PAD;
-  __shared__ __attribute__((aligned(16))) T Pt[KB * LDC];    // [key][q]
-  __shared__ __attribute__((aligned(16))) T dSt[KB * LDC];   // [key][q]
-  __shared__ __attribute__((aligned(16))) T dOt[HD * LDC];   // [d][q]
-  __shared__ __attribute__((aligned(16))) T Qt[HD * LDC];    // [d][q]
+  __shared__ __attribute__((aligned(16))) float Pt[KB * LDC];    // [key][q]
+  __shared__ __attribute__((aligned(16))) float dSt[KB * LDC];   // [key][q]
+  __shared__ __attribute__((aligned(16))) float dOt[HD * LDC];   // [d][q]
+  __shared__ __attribute__((aligned(16))) float Qt[HD * LDC];    // [d][q]
   int kb, h, b;
-  attn_block((L + KB - 1) / KB, H, kb, h, b);
+  attn_block(blocks_per_head(L, NW), H, kb, h, b);
   const int k0 = kb * KB;
-  const int LP = (L + 31) & ~31;  // multiple of the bf16 MFMA K (32)
+  const int LP = attn_lp(L);
   const long row_ld = 3L * H * HD;
-  const T* qbase = qkv + (long)b * L * row_ld + h * HD;
+  const float* qbase = qkv + (long)b * L * row_ld + h * HD;
   const float* pb = probs + (((long)b * H + h) * L) * L;
-  const T* dsb = dS_g + (((long)b * H + h) * L) * LP;
+  const float* dsb = dS_g + (((long)b * H + h) * L) * LP;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   f32x4 dv[HD / 16], dk[HD / 16];
 #pragma unroll
@@ -408,13 +425,13 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(con
   // the P / dS reads are key-contiguous across lanes (coalesced rows of [q][key]) and land in
   // LDS as one [key][q] vector store each; the dO / Q slices of the chunk are NV vectors per
   // thread.  The next chunk's loads are issued into registers before this chunk's MFMAs.
-  typedef typename Vec16<T>::type V;
-  constexpr int VEC = Vec16<T>::N, VPR = HD / VEC, NTH = NW * 64;
+  typedef typename Vec16<float>::type V;
+  constexpr int VEC = Vec16<float>::N, VPR = HD / VEC, NTH = NW * 64;
   constexpr int QG = 8, NV = QC * VPR / NTH;
   static_assert(KB * QC == NTH * QG && NV * NTH == QC * VPR, "chunk staging shape");
   const int kk = threadIdx.x % KB, qg = threadIdx.x / KB;
   float pr[QG];
-  T dsr[QG];
+  float dsr[QG];
   V dov[NV], qv[NV];
   auto fetch = [&](int qc) {
     const int key = k0 + kk;
@@ -423,7 +440,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(con
       const int q = qc + qg * QG + u;
       const bool ok = key < L && q < L;
       pr[u] = ok ? pb[(long)q * L + key] : 0.f;
-      dsr[u] = ok ? dsb[(long)q * LP + key] : from_f<T>(0.f);
+      dsr[u] = ok ? dsb[(long)q * LP + key] : 0.f;
     }
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
@@ -445,7 +462,7 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(con
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float v = pr[w * VEC + j];
-        pv[j] = from_f<T>(__builtin_signbitf(v) ? 0.f : v * keep_scale);  // P'
+        pv[j] = __builtin_signbitf(v) ? 0.f : v * keep_scale;  // P'
         sv[j] = dsr[w * VEC + j];
       }
       *(V*)(Pt + kk * LDC + qg * QG + w * VEC) = pv;
@@ -454,13 +471,13 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(con
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
       const int i = threadIdx.x + n * NTH, r = i / VPR, c = (i - r * VPR) * VEC;
-      put_row_vec<T, true>(dOt, LDC, r, c, dov[n]);
-      put_row_vec<T, true>(Qt, LDC, r, c, qv[n]);
+      put_row_vec<float, true>(dOt, LDC, r, c, dov[n]);
+      put_row_vec<float, true>(Qt, LDC, r, c, qv[n]);
     }
     __syncthreads();
     if (qc + QC < L) fetch(qc + QC);
-    const T* ap = Pt + (wid * 16 + (lane & 15)) * LDC + (lane >> 4) * Op::FRAG;
-    const T* as = dSt + (wid * 16 + (lane & 15)) * LDC + (lane >> 4) * Op::FRAG;
+    const float* ap = Pt + (wid * 16 + (lane & 15)) * LDC + (lane >> 4) * Op::FRAG;
+    const float* as = dSt + (wid * 16 + (lane & 15)) * LDC + (lane >> 4) * Op::FRAG;
 #pragma unroll
     for (int k = 0; k < QC; k += Op::KS) {
       const typename Op::frag_t fp = Op::ld(ap + k), fs = Op::ld(as + k);
@@ -479,9 +496,9 @@ __global__ __launch_bounds__(AttnCfg<T>::NW * 64, 2) void attn_bwd_kv_kernel(con
     for (int r = 0; r < 4; ++r) {
       const int key = k0 + wid * 16 + (lane >> 4) * 4 + r;
       if (key < L) {
-        T* row = dqkv + ((long)b * L + key) * 3 * H * HD + h * HD + j * 16 + (lane & 15);
-        row[(long)H * HD] = from_f<T>(dk[j][r] * scale);
-        row[2L * H * HD] = from_f<T>(dv[j][r]);
+        float* row = dqkv + ((long)b * L + key) * 3 * H * HD + h * HD + j * 16 + (lane & 15);
+        row[(long)H * HD] = dk[j][r] * scale;
+        row[2L * H * HD] = dv[j][r];
       }
     }
 }
@@ -531,6 +548,153 @@ __device__ __forceinline__ void store4(T* dst, float a, float b, float c, float 
   *(uint2*)dst = pk.u;
 }
 
+// LDS layouts of the 16-bit kernels, as byte offsets from the dynamic LDS base: functions of
+// (L, NW, sizeof(T)) that the kernel's carve-up and the launch's byte count both read.
+// Every member starts on a 16-B boundary (LP is a multiple of 32).
+//
+// Query-block kernels (attn_fwd16_kernel, attn_bwd_q16_kernel, attn_bwd_q16_lse_kernel):
+struct QBlockLds {
+  int rows;      // [LP][LDR] T  A operand rows of the first product (K; V in the backward)
+  int tr;        // [LP][LDT] T  transposed reads (V; K in the backward)
+  int madd;      // [LP] float   additive key mask.  attn_bwd_q16_kernel reads the mask from the
+                 // saved probabilities and leaves this unused; it stays in that kernel's layout
+                 // because the launch's byte count decides the blocks per CU
+  int pscr;      // [NW][16][LDP] float  per-wave probability-tile transpose (L % 4 != 0)
+  int end;
+  __host__ __device__ constexpr QBlockLds(int L, int nw, int esz)
+      : rows(0), tr(rows + attn_lp(L) * LDR * esz), madd(tr + attn_lp(L) * LDT * esz),
+        pscr(madd + attn_lp(L) * 4), end(pscr + nw * 16 * LDP * 4) {}
+  // P-saving launches carry the transpose scratch; the flash-style ones (no probabilities)
+  // stop before it
+  __host__ __device__ constexpr size_t bytes(bool prob_tiles) const {
+    return prob_tiles ? end : pscr;
+  }
+};
+// Key-block kernels (attn_bwd_kv16_kernel, attn_bwd_kv16_lse_kernel):
+struct KBlockLds {
+  int q;         // [LP][LDT] T  the head's Q rows
+  int dout;      // [LP][LDT] T  the head's dO rows
+  int lse;       // [LP] float   row log-sum-exp, 0 beyond L   (flash-style only)
+  int d;         // [LP] float   D = rowsum(dO o O)            (flash-style only)
+  int end;
+  __host__ __device__ constexpr KBlockLds(int L, int esz)
+      : q(0), dout(q + attn_lp(L) * LDT * esz), lse(dout + attn_lp(L) * LDT * esz),
+        d(lse + attn_lp(L) * 4), end(d + attn_lp(L) * 4) {}
+  __host__ __device__ constexpr size_t bytes(bool flash) const { return flash ? end : lse; }
+};
+static_assert(QBlockLds(16 * MAXKT, 16, 2).end <= 160 * 1024 &&
+                  KBlockLds(16 * MAXKT, 2).end <= 160 * 1024,
+              "the largest 16-bit attention block (L = 256, 16 waves) fits the 160 KB of LDS");
+
+// A thread's place in a 16-bit kernel.  The block owns rows r0 .. r0 + 16*NW - 1 (queries; keys
+// in the kv kernels) of head h of batch b; lane (col = lane & 15, g = lane >> 4) of wave wid
+// holds row `row` on its MFMA column.  idle: a wave of padding rows, which stages and leaves
+// after the block's one barrier.
+template <int NW>
+struct Place16 {
+  int h, b, r0, wid, col, g, row;
+  bool idle;
+  __device__ __forceinline__ Place16(int L, int H) {
+    int blk;
+    attn_block(blocks_per_head(L, NW), H, blk, h, b);
+    r0 = blk * NW * 16;
+    const int lane = threadIdx.x & 63;
+    wid = threadIdx.x >> 6;
+    col = lane & 15;
+    g = lane >> 4;
+    row = r0 + wid * 16 + col;
+    idle = r0 + wid * 16 >= L;
+  }
+};
+
+// sum over the four lanes (g = 0..3) that share a column
+__device__ __forceinline__ float column_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+// The lane's two 8-element MFMA operand fragments of a 64-element head row in HBM (elements
+// k*32 + g*8 ..); zero when the row is padding.  (The flash-style backward kernels' five
+// loads.  attn_fwd16_kernel and attn_bwd_q16_kernel keep the same loop in their bodies: through
+// this function their instruction schedule moved and the BERT-shape rows slowed by 1-2 %.)
+template <typename T>
+__device__ __forceinline__ void load_row_frags(typename MfmaOp<T>::frag_t (&f)[2], const T* row,
+                                               bool ok, int g) {
+  typedef typename MfmaOp<T>::frag_t F;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    f[k] = F{};
+    if (ok) f[k] = *(const F*)(row + k * 32 + g * 8);
+  }
+}
+// acc += tile[row][0..63] (an LDS row image, leading dimension ld, as the A operand) x the
+// lane's two fragments: one 16 x 16 tile of S^T / dP^T (or S / dP' in the kv kernel).
+template <typename T>
+__device__ __forceinline__ f32x4 rows_x_frags(const T* tile, int ld, int row, int g,
+                                              const typename MfmaOp<T>::frag_t (&f)[2],
+                                              f32x4 acc) {
+  typedef MfmaOp<T> Op;
+  const T* a = tile + row * ld + g * 8;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) acc = Op::mma(Op::ld(a + k * 32), f[k], acc);
+  return acc;
+}
+// acc += tile^T[dt*16 ..][k] x f for 16-column block dt of the head dim, where the 8 k elements
+// are rows ra .. ra+3 and rb .. rb+3 of the [..][LDT] tile (the callers' row permutations
+// differ: they are the k order in which each formed f).
+template <typename T>
+__device__ __forceinline__ f32x4 tr_mma(const T* tile, int ra, int rb, int dt,
+                                        const typename MfmaOp<T>::frag_t& f, f32x4 acc) {
+  return MfmaOp<T>::mma(join_frag<T>(tr_read4(tile, ra, dt * 16), tr_read4(tile, rb, dt * 16)), f,
+                        acc);
+}
+// o^T += tile^T x f over the head dim (O^T += V^T P'^T, dQ^T += K^T dS^T)
+template <typename T>
+__device__ __forceinline__ void tr_rows_x_frag(f32x4 (&o)[HD / 16], const T* tile, int ra, int rb,
+                                               const typename MfmaOp<T>::frag_t& f) {
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt) o[dt] = tr_mma<T>(tile, ra, rb, dt, f, o[dt]);
+}
+// the kv kernels' pair dV^T += dO^T P', dK^T += Q^T dS over one 32-query chunk
+template <typename T>
+__device__ __forceinline__ void dv_dk_step(f32x4 (&dv)[HD / 16], const T* Os,
+                                           const typename MfmaOp<T>::frag_t& pf,
+                                           f32x4 (&dk)[HD / 16], const T* Qs,
+                                           const typename MfmaOp<T>::frag_t& sf, int ra, int rb) {
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt) {
+    dv[dt] = tr_mma<T>(Os, ra, rb, dt, pf, dv[dt]);
+    dk[dt] = tr_mma<T>(Qs, ra, rb, dt, sf, dk[dt]);
+  }
+}
+__device__ __forceinline__ void zero_tiles(f32x4 (&o)[HD / 16]) {
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// the lane's 4 elements of 16-column block dt of a 64-element output row, times scale
+template <typename T>
+__device__ __forceinline__ void store_tile(T* row, int g, int dt, const f32x4& o,
+                                           float scale = 1.f) {
+  store4<T>(row + dt * 16 + g * 4, o[0] * scale, o[1] * scale, o[2] * scale, o[3] * scale);
+}
+// a row of out or dQ
+template <typename T>
+__device__ __forceinline__ void store_row(T* row, int g, const f32x4 (&o)[HD / 16],
+                                          float scale = 1.f) {
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt) store_tile<T>(row, g, dt, o[dt], scale);
+}
+// the dK (scaled) and dV rows of a key into dqkv's [.., 3, H, 64] row
+template <typename T>
+__device__ __forceinline__ void store_dk_dv(T* row, int H, int g, const f32x4 (&dk)[HD / 16],
+                                            const f32x4 (&dv)[HD / 16], float scale) {
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; ++dt) {
+    store_tile<T>(row + (long)H * HD, g, dt, dk[dt], scale);
+    store_tile<T>(row + 2L * H * HD, g, dt, dv[dt]);
+  }
+}
+
 template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kernel(
     const T* __restrict__ qkv, const int64_t* __restrict__ mask, const float* __restrict__ bias,
@@ -540,21 +704,17 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
   typedef MfmaOp<T> Op;
   typedef typename Op::frag_t F;
   static_assert(Op::FRAG == 8 && Op::KS == 32, "16-bit MFMA 16x16x32 operands");
-  constexpr int QB = NW * 16;
-  const int LP = (L + 31) & ~31;
+  const int LP = attn_lp(L);
   const int nkt = LP / 16;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Ks = (T*)smem_raw;               // [LP][LDR]  A operand rows of S^T
-  T* Vs = Ks + LP * LDR;              // [LP][LDT]  transposed reads for V^T
-  float* madd = (float*)(Vs + LP * LDT);   // [LP] additive key mask
-  int qb, h, b;
-  attn_block((L + QB - 1) / QB, H, qb, h, b);
-  const int q0 = qb * QB;
+  const QBlockLds lds(L, NW, sizeof(T));
+  T* Ks = (T*)(smem_raw + lds.rows);         // A operand rows of S^T
+  T* Vs = (T*)(smem_raw + lds.tr);           // transposed reads for V^T
+  float* madd = (float*)(smem_raw + lds.madd);
+  const Place16<NW> at(L, H);
+  const int h = at.h, b = at.b, q0 = at.r0, wid = at.wid, ql = at.col, g = at.g, q = at.row;
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, ql = lane & 15, g = lane >> 4;
-  const int q = q0 + wid * 16 + ql;
-  const bool idle = q0 + wid * 16 >= L;   // a wave of padding queries: stage, then leave
   F qf[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -563,10 +723,9 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
   }
   stage_pair<T, 4, false, false>(Ks, LDR, base + (long)H * HD, Vs, LDT, base + 2L * H * HD,
                                  row_ld, LP, L, NW * 64);
-  for (int k = threadIdx.x; k < LP; k += NW * 64)
-    madd[k] = k < L ? (mask && mask[(long)b * L + k] == 0 ? MASK_NEG : 0.f) : -INFINITY;
+  for (int k = threadIdx.x; k < LP; k += NW * 64) madd[k] = key_mask_add(mask, b, L, k);
   __syncthreads();   // the only barrier: idle waves may leave after it
-  if (idle) return;
+  if (at.idle) return;
   // s[j][r] = S[q][j*16 + g*4 + r]
   f32x4 s[MAXKT];
   float mx = -INFINITY;
@@ -574,9 +733,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
   for (int j = 0; j < MAXKT; ++j) {
     s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (j >= nkt) continue;
-    const T* a = Ks + (j * 16 + ql) * LDR + g * 8;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) s[j] = Op::mma(Op::ld(a + k * 32), qf[k], s[j]);
+    s[j] = rows_x_frags<T>(Ks, LDR, j * 16 + ql, g, qf, s[j]);
     const f32x4 ma = *(const f32x4*)(madd + j * 16 + g * 4);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -601,8 +758,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
       sum += s[j][r];
     }
   }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
+  sum = column_sum(sum);
   const float inv = 1.f / sum;
   // flash-style save (mmdx_attention_fwd_lse): the row log-sum-exp instead of P
   if (lse && g == 0 && q < L) lse[((long)b * H + h) * L + q] = mx + __logf(sum);
@@ -610,12 +766,12 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
   const bool vec_p = (L & 3) == 0;
   // L % 4 != 0: the lane's 4 keys are not a 16-B aligned run of a row; the wave transposes
   // each 16 x 16 tile through its LDS scratch so a store covers 64 contiguous bytes of 4 rows
-  float* pscr = madd + LP + wid * 16 * LDP;
+  float* pscr = (float*)(smem_raw + lds.pscr) + wid * 16 * LDP;
+  const uint64_t rb0 = dropout_stream_base(seed, ctr);
+  if (rng_out && blockIdx.x == 0 && threadIdx.x == 0) rng_out[0] = rb0;  // for the backward
   const bool drop = p_drop > 0.f;
   const float keep_scale = drop ? 1.f / (1.f - p_drop) : 1.f;
-  const uint64_t rb0 = seed * 0x9E3779B97F4A7C15ULL + (ctr ? ctr[0] << 32 : 0ull);
-  if (rng_out && blockIdx.x == 0 && threadIdx.x == 0) rng_out[0] = rb0;  // for the backward
-  const uint64_t rbase = drop ? rb0 + (((uint64_t)b * H + h) * L) * (uint64_t)L : 0ull;
+  const uint64_t rbase = drop ? head_stream(rb0, b, h, H, L) : 0ull;
   F pf[MAXKT / 2];
 #pragma unroll
   for (int j = 0; j < MAXKT; ++j) {
@@ -626,10 +782,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
       const int key = j * 16 + g * 4 + r;
       const float p = s[j][r] * inv;
       bool keep = true;
-      if (drop) {
-        const float u = (attn_hash64(rbase + (uint64_t)q * L + key) >> 8) * (1.f / 16777216.f);
-        keep = u >= p_drop;
-      }
+      if (drop) keep = dropout_keep(rbase, (uint64_t)q * L + key, p_drop);
       pf[j >> 1][(j & 1) * 4 + r] = from_f<T>(keep ? p * keep_scale : 0.f);
       pv[r] = keep ? p : -p;
     }
@@ -651,24 +804,13 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW) void attn_fwd16_kern
   }
   // O^T[d][q] = sum_key V^T[d][key] P'^T[key][q]
   f32x4 o[HD / 16];
-#pragma unroll
-  for (int dt = 0; dt < HD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tiles(o);
 #pragma unroll
   for (int t = 0; t < MAXKT / 2; ++t) {
     if (2 * t >= nkt) continue;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      const F vf = join_frag<T>(tr_read4(Vs, 2 * t * 16 + g * 4, dt * 16),
-                                tr_read4(Vs, (2 * t + 1) * 16 + g * 4, dt * 16));
-      o[dt] = Op::mma(vf, pf[t], o[dt]);
-    }
+    tr_rows_x_frag<T>(o, Vs, 2 * t * 16 + g * 4, (2 * t + 1) * 16 + g * 4, pf[t]);
   }
-  if (q < L) {
-    T* orow = out + ((long)b * L + q) * H * HD + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt)
-      store4<T>(orow + dt * 16 + g * 4, o[dt][0], o[dt][1], o[dt][2], o[dt][3]);
-  }
+  if (q < L) store_row<T>(out + ((long)b * L + q) * H * HD + h * HD, g, o);
 }
 
 // Backward A (16-bit): dP^T = V dO^T, dS = P o (dP - rowsum(P o dP)) -> dS_g [B,H,L,LP],
@@ -682,20 +824,16 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
     int L, int H, float scale, float keep_scale, T* __restrict__ dS_g, T* __restrict__ dqkv) {
   typedef MfmaOp<T> Op;
   typedef typename Op::frag_t F;
-  constexpr int QB = NW * 16;
-  const int LP = (L + 31) & ~31;
+  const int LP = attn_lp(L);
   const int nkt = LP / 16;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Vs = (T*)smem_raw;               // [LP][LDR]  A operand rows of dP^T
-  T* Ks = Vs + LP * LDR;              // [LP][LDT]  transposed reads for K^T
-  int qb, h, b;
-  attn_block((L + QB - 1) / QB, H, qb, h, b);
-  const int q0 = qb * QB;
+  const QBlockLds lds(L, NW, sizeof(T));
+  T* Vs = (T*)(smem_raw + lds.rows);         // A operand rows of dP^T
+  T* Ks = (T*)(smem_raw + lds.tr);           // transposed reads for K^T
+  const Place16<NW> at(L, H);
+  const int h = at.h, b = at.b, q0 = at.r0, wid = at.wid, ql = at.col, g = at.g, q = at.row;
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, ql = lane & 15, g = lane >> 4;
-  const int q = q0 + wid * 16 + ql;
-  const bool idle = q0 + wid * 16 >= L;   // a wave of padding queries: stage, then leave
   F of[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -705,7 +843,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
   stage_pair<T, 4, false, false>(Vs, LDR, base + 2L * H * HD, Ks, LDT, base + (long)H * HD,
                                  row_ld, LP, L, NW * 64);
   __syncthreads();   // the only barrier: idle waves may leave after it
-  if (idle) return;
+  if (at.idle) return;
   // saved probabilities P[q][j*16 + g*4 + r] -> pv[j][r]: one 16-B load per tile when
   // L % 4 == 0; otherwise 4 loads of 64 contiguous bytes of 4 rows each, transposed through
   // the wave's LDS scratch (in-order LDS within the wave: no barrier)
@@ -719,7 +857,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
         pv[j] = *(const f32x4*)(pbase + (long)q * L + j * 16 + g * 4);
     }
   } else {
-    float* pscr = (float*)(Ks + LP * LDT) + LP + wid * 16 * LDP;
+    float* pscr = (float*)(smem_raw + lds.pscr) + wid * 16 * LDP;
 #pragma unroll
     for (int j = 0; j < MAXKT; ++j) {
       pv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -742,10 +880,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
   // dP'[q][j*16 + g*4 + r] -> dP = keep * dP' / (1 - p); dropped elements are saved with the
   // sign bit set
   auto dp_tile = [&](int j) {
-    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-    const T* a = Vs + (j * 16 + ql) * LDR + g * 8;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) t = Op::mma(Op::ld(a + k * 32), of[k], t);
+    f32x4 t = rows_x_frags<T>(Vs, LDR, j * 16 + ql, g, of, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
     for (int r = 0; r < 4; ++r) t[r] = __builtin_signbitf(pv[j][r]) ? 0.f : t[r] * keep_scale;
     return t;
@@ -758,13 +893,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) dot += fabsf(pv[j][r]) * t[r];
   }
-  dot += __shfl_xor(dot, 16, 64);
-  dot += __shfl_xor(dot, 32, 64);
+  dot = column_sum(dot);
   T* dsrow = dS_g + ((((long)b * H + h) * L) + q) * LP;
   // dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q]
   f32x4 o[HD / 16];
-#pragma unroll
-  for (int dt = 0; dt < HD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tiles(o);
 #pragma unroll
   for (int t = 0; t < MAXKT / 2; ++t) {
     if (2 * t >= nkt) continue;
@@ -782,20 +915,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_kernel(
       }
       if (q < L) store4<T>(dsrow + j * 16 + g * 4, ds[0], ds[1], ds[2], ds[3]);
     }
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      const F kf = join_frag<T>(tr_read4(Ks, 2 * t * 16 + g * 4, dt * 16),
-                                tr_read4(Ks, (2 * t + 1) * 16 + g * 4, dt * 16));
-      o[dt] = Op::mma(kf, df, o[dt]);
-    }
+    tr_rows_x_frag<T>(o, Ks, 2 * t * 16 + g * 4, (2 * t + 1) * 16 + g * 4, df);
   }
-  if (q < L) {
-    T* drow = dqkv + ((long)b * L + q) * 3 * H * HD + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt)
-      store4<T>(drow + dt * 16 + g * 4, o[dt][0] * scale, o[dt][1] * scale, o[dt][2] * scale,
-                o[dt][3] * scale);
-  }
+  if (q < L) store_row<T>(dqkv + ((long)b * L + q) * 3 * H * HD + h * HD, g, o, scale);
 }
 
 // Backward B (16-bit), swapped products, per key block of 16*NW keys, one key
@@ -811,29 +933,25 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_kernel(
     T* __restrict__ dqkv) {
   typedef MfmaOp<T> Op;
   typedef typename Op::frag_t F;
-  constexpr int KB = NW * 16;
-  const int LP = (L + 31) & ~31;
+  const int LP = attn_lp(L);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Qs = (T*)smem_raw;               // [LP][LDT]
-  T* Os = Qs + LP * LDT;              // [LP][LDT]  dO
-  int kb, h, b;
-  attn_block((L + KB - 1) / KB, H, kb, h, b);
-  const int k0 = kb * KB;
+  const KBlockLds lds(L, sizeof(T));
+  T* Qs = (T*)(smem_raw + lds.q);
+  T* Os = (T*)(smem_raw + lds.dout);
+  const Place16<NW> at(L, H);
+  const int h = at.h, b = at.b, g = at.g, key = at.row;
   const long row_ld = 3L * H * HD;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, kl = lane & 15, g = lane >> 4;
-  const int key = k0 + wid * 16 + kl;
-  const bool idle = k0 + wid * 16 >= L;   // a wave of padding keys: stage, then leave
   stage_rows<T, 4, false>(Qs, LDT, qkv + (long)b * L * row_ld + h * HD, row_ld, LP, L, NW * 64);
   stage_rows<T, 4, false>(Os, LDT, dout + (long)b * L * H * HD + h * HD, (long)H * HD, LP, L,
                           NW * 64);
   __syncthreads();   // the only barrier
-  if (idle) return;
+  if (at.idle) return;
   const float* pb = probs + (((long)b * H + h) * L) * L;
   const T* dsb = dS_g + (((long)b * H + h) * L) * LP;
   const bool kok = key < L;
   f32x4 dv[HD / 16], dk[HD / 16];
-#pragma unroll
-  for (int dt = 0; dt < HD / 16; ++dt) dv[dt] = dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tiles(dv);
+  zero_tiles(dk);
   for (int qs = 0; qs < LP; qs += 32) {
     F pf, sf;
 #pragma unroll
@@ -844,26 +962,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_kernel(
       pf[e] = from_f<T>(__builtin_signbitf(v) ? 0.f : v * keep_scale);  // P'
       sf[e] = ok ? dsb[(long)q * LP + key] : from_f<T>(0.f);
     }
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      const F of = join_frag<T>(tr_read4(Os, qs + g * 8, dt * 16),
-                                tr_read4(Os, qs + g * 8 + 4, dt * 16));
-      dv[dt] = Op::mma(of, pf, dv[dt]);
-      const F qf = join_frag<T>(tr_read4(Qs, qs + g * 8, dt * 16),
-                                tr_read4(Qs, qs + g * 8 + 4, dt * 16));
-      dk[dt] = Op::mma(qf, sf, dk[dt]);
-    }
+    dv_dk_step<T>(dv, Os, pf, dk, Qs, sf, qs + g * 8, qs + g * 8 + 4);
   }
-  if (kok) {
-    T* row = dqkv + ((long)b * L + key) * 3 * H * HD + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      store4<T>(row + (long)H * HD + dt * 16 + g * 4, dk[dt][0] * scale, dk[dt][1] * scale,
-                dk[dt][2] * scale, dk[dt][3] * scale);
-      store4<T>(row + 2L * H * HD + dt * 16 + g * 4, dv[dt][0], dv[dt][1], dv[dt][2],
-                dv[dt][3]);
-    }
-  }
+  if (kok) store_dk_dv<T>(dqkv + ((long)b * L + key) * 3 * H * HD + h * HD, H, g, dk, dv, scale);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -889,51 +990,38 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
     int L, int H, float scale, float p_drop, float* __restrict__ Dg, T* __restrict__ dqkv) {
   typedef MfmaOp<T> Op;
   typedef typename Op::frag_t F;
-  constexpr int QB = NW * 16;
-  const int LP = (L + 31) & ~31;
+  const int LP = attn_lp(L);
   const int nkt = LP / 16;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Vs = (T*)smem_raw;               // [LP][LDR]  A operand rows of dP^T
-  T* Ks = Vs + LP * LDR;              // [LP][LDT]  A operand rows of S^T / transposed K^T
-  float* madd = (float*)(Ks + LP * LDT);   // [LP]
-  int qb, h, b;
-  attn_block((L + QB - 1) / QB, H, qb, h, b);
-  const int q0 = qb * QB;
+  const QBlockLds lds(L, NW, sizeof(T));
+  T* Vs = (T*)(smem_raw + lds.rows);         // A operand rows of dP^T
+  T* Ks = (T*)(smem_raw + lds.tr);           // A operand rows of S^T / transposed K^T
+  float* madd = (float*)(smem_raw + lds.madd);
+  const Place16<NW> at(L, H);
+  const int h = at.h, b = at.b, ql = at.col, g = at.g, q = at.row;
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, ql = lane & 15, g = lane >> 4;
-  const int q = q0 + wid * 16 + ql;
-  const bool idle = q0 + wid * 16 >= L;
-  F qf[2], of[2];
+  const long orow = ((long)b * L + q) * H * HD + h * HD;
+  F qf[2], of[2], ov[2];
+  load_row_frags<T>(qf, base + (long)q * row_ld, q < L, g);
+  load_row_frags<T>(of, dout + orow, q < L, g);
+  load_row_frags<T>(ov, outp + orow, q < L, g);
   float dot = 0.f;
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    qf[k] = of[k] = F{};
-    if (q < L) {
-      qf[k] = *(const F*)(base + (long)q * row_ld + k * 32 + g * 8);
-      const long orow = ((long)b * L + q) * H * HD + h * HD + k * 32 + g * 8;
-      of[k] = *(const F*)(dout + orow);
-      const F ov = *(const F*)(outp + orow);
+  for (int k = 0; k < 2; ++k)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) dot += (float)of[k][e] * (float)ov[e];
-    }
-  }
-  dot += __shfl_xor(dot, 16, 64);
-  dot += __shfl_xor(dot, 32, 64);
+    for (int e = 0; e < 8; ++e) dot += (float)of[k][e] * (float)ov[k][e];
+  dot = column_sum(dot);
   stage_pair<T, 4, false, false>(Vs, LDR, base + 2L * H * HD, Ks, LDT, base + (long)H * HD,
                                  row_ld, LP, L, NW * 64);
-  for (int k = threadIdx.x; k < LP; k += NW * 64)
-    madd[k] = k < L ? (mask && mask[(long)b * L + k] == 0 ? MASK_NEG : 0.f) : -INFINITY;
+  for (int k = threadIdx.x; k < LP; k += NW * 64) madd[k] = key_mask_add(mask, b, L, k);
   __syncthreads();   // the only barrier
-  if (idle) return;
+  if (at.idle) return;
   if (g == 0 && q < L) Dg[((long)b * H + h) * L + q] = dot;
   const float lq = q < L ? lse[((long)b * H + h) * L + q] : 0.f;
-  const bool drop = p_drop > 0.f;
-  const float keep_scale = drop ? 1.f / (1.f - p_drop) : 1.f;
-  const uint64_t rbase = drop ? rng[0] + (((uint64_t)b * H + h) * L) * (uint64_t)L : 0ull;
+  const HeadDropout dr(p_drop, p_drop > 0.f ? rng[0] : 0ull, b, h, H, L);
   f32x4 o[HD / 16];
-#pragma unroll
-  for (int dt = 0; dt < HD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tiles(o);
 #pragma unroll
   for (int t = 0; t < MAXKT / 2; ++t) {
     if (2 * t >= nkt) continue;
@@ -941,42 +1029,21 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
       const int j = 2 * t + h2;
-      f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f}, tp = st;
-      const T* ak = Ks + (j * 16 + ql) * LDT + g * 8;
-      const T* av = Vs + (j * 16 + ql) * LDR + g * 8;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        st = Op::mma(Op::ld(ak + k * 32), qf[k], st);
-        tp = Op::mma(Op::ld(av + k * 32), of[k], tp);
-      }
+      const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 st = rows_x_frags<T>(Ks, LDT, j * 16 + ql, g, qf, z);
+      const f32x4 tp = rows_x_frags<T>(Vs, LDR, j * 16 + ql, g, of, z);
       const f32x4 ma = *(const f32x4*)(madd + j * 16 + g * 4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = j * 16 + g * 4 + r;
         const float p = __expf(st[r] * scale + ma[r] - lq);
-        bool keep = true;
-        if (drop) {
-          const float u = (attn_hash64(rbase + (uint64_t)q * L + key) >> 8) * (1.f / 16777216.f);
-          keep = u >= p_drop;
-        }
-        const float dp = keep ? tp[r] * keep_scale : 0.f;
+        const float dp = dr.keep(q, key) ? tp[r] * dr.keep_scale : 0.f;
         df[h2 * 4 + r] = from_f<T>(p * (dp - dot));
       }
     }
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      const F kf = join_frag<T>(tr_read4(Ks, 2 * t * 16 + g * 4, dt * 16),
-                                tr_read4(Ks, (2 * t + 1) * 16 + g * 4, dt * 16));
-      o[dt] = Op::mma(kf, df, o[dt]);
-    }
+    tr_rows_x_frag<T>(o, Ks, 2 * t * 16 + g * 4, (2 * t + 1) * 16 + g * 4, df);
   }
-  if (q < L) {
-    T* drow = dqkv + ((long)b * L + q) * 3 * H * HD + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt)
-      store4<T>(drow + dt * 16 + g * 4, o[dt][0] * scale, o[dt][1] * scale, o[dt][2] * scale,
-                o[dt][3] * scale);
-  }
+  if (q < L) store_row<T>(dqkv + ((long)b * L + q) * 3 * H * HD + h * HD, g, o, scale);
 }
 
 template <typename T, int NW>
@@ -986,31 +1053,21 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_lse_kernel(
     int L, int H, float scale, float p_drop, T* __restrict__ dqkv) {
   typedef MfmaOp<T> Op;
   typedef typename Op::frag_t F;
-  constexpr int KB = NW * 16;
-  const int LP = (L + 31) & ~31;
+  const int LP = attn_lp(L);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Qs = (T*)smem_raw;               // [LP][LDT]
-  T* Os = Qs + LP * LDT;              // [LP][LDT]  dO
-  float* ls = (float*)(Os + LP * LDT);   // [LP] lse (0 beyond L)
-  float* ds_ = ls + LP;                  // [LP] D
-  int kb, h, b;
-  attn_block((L + KB - 1) / KB, H, kb, h, b);
-  const int k0 = kb * KB;
+  const KBlockLds lds(L, sizeof(T));
+  T* Qs = (T*)(smem_raw + lds.q);
+  T* Os = (T*)(smem_raw + lds.dout);
+  float* ls = (float*)(smem_raw + lds.lse);
+  float* ds_ = (float*)(smem_raw + lds.d);
+  const Place16<NW> at(L, H);
+  const int h = at.h, b = at.b, kl = at.col, g = at.g, key = at.row;
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, kl = lane & 15, g = lane >> 4;
-  const int key = k0 + wid * 16 + kl;
-  const bool idle = k0 + wid * 16 >= L;
   const bool kok = key < L;
   F kf[2], vf[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    kf[k] = vf[k] = F{};
-    if (kok) {
-      kf[k] = *(const F*)(base + (long)key * row_ld + (long)H * HD + k * 32 + g * 8);
-      vf[k] = *(const F*)(base + (long)key * row_ld + 2L * H * HD + k * 32 + g * 8);
-    }
-  }
+  load_row_frags<T>(kf, base + (long)key * row_ld + (long)H * HD, kok, g);
+  load_row_frags<T>(vf, base + (long)key * row_ld + 2L * H * HD, kok, g);
   stage_rows<T, 4, false>(Qs, LDT, base, row_ld, LP, L, NW * 64);
   stage_rows<T, 4, false>(Os, LDT, dout + (long)b * L * H * HD + h * HD, (long)H * HD, LP, L,
                           NW * 64);
@@ -1020,69 +1077,34 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_lse_kernel(
     ds_[i] = i < L ? Dg[hq + i] : 0.f;
   }
   __syncthreads();   // the only barrier
-  if (idle) return;
-  const float mk = kok ? (mask && mask[(long)b * L + key] == 0 ? MASK_NEG : 0.f) : -INFINITY;
-  const bool drop = p_drop > 0.f;
-  const float keep_scale = drop ? 1.f / (1.f - p_drop) : 1.f;
-  const uint64_t rbase = drop ? rng[0] + (uint64_t)hq * (uint64_t)L : 0ull;
+  if (at.idle) return;
+  const float mk = key_mask_add(mask, b, L, key);
+  const HeadDropout dr(p_drop, p_drop > 0.f ? rng[0] : 0ull, b, h, H, L);
   f32x4 dv[HD / 16], dk[HD / 16];
-#pragma unroll
-  for (int dt = 0; dt < HD / 16; ++dt) dv[dt] = dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tiles(dv);
+  zero_tiles(dk);
   for (int qs = 0; qs < LP; qs += 32) {
     F pf, sf;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f}, tp = st;
-      const T* aq = Qs + (qs + 16 * u + kl) * LDT + g * 8;
-      const T* ao = Os + (qs + 16 * u + kl) * LDT + g * 8;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        st = Op::mma(Op::ld(aq + k * 32), kf[k], st);   // S[q][key]
-        tp = Op::mma(Op::ld(ao + k * 32), vf[k], tp);   // dP'[q][key]
-      }
+      const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 st = rows_x_frags<T>(Qs, LDT, qs + 16 * u + kl, g, kf, z);   // S[q][key]
+      const f32x4 tp = rows_x_frags<T>(Os, LDT, qs + 16 * u + kl, g, vf, z);   // dP'[q][key]
       const int qr0 = qs + 16 * u + g * 4;
       const f32x4 lq = *(const f32x4*)(ls + qr0);
       const f32x4 dq = *(const f32x4*)(ds_ + qr0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int qq = qr0 + r;
         const float p = __expf(st[r] * scale + mk - lq[r]);
-        bool keep = true;
-        if (drop) {
-          const float uu =
-              (attn_hash64(rbase + (uint64_t)qq * L + key) >> 8) * (1.f / 16777216.f);
-          keep = uu >= p_drop;
-        }
-        const float dp = keep ? tp[r] * keep_scale : 0.f;
-        pf[u * 4 + r] = from_f<T>(keep ? p * keep_scale : 0.f);
+        const bool keep = dr.keep(qr0 + r, key);
+        const float dp = keep ? tp[r] * dr.keep_scale : 0.f;
+        pf[u * 4 + r] = from_f<T>(keep ? p * dr.keep_scale : 0.f);
         sf[u * 4 + r] = from_f<T>(p * (dp - dq[r]));
       }
     }
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      const F of = join_frag<T>(tr_read4(Os, qs + g * 4, dt * 16),
-                                tr_read4(Os, qs + 16 + g * 4, dt * 16));
-      dv[dt] = Op::mma(of, pf, dv[dt]);
-      const F qf = join_frag<T>(tr_read4(Qs, qs + g * 4, dt * 16),
-                                tr_read4(Qs, qs + 16 + g * 4, dt * 16));
-      dk[dt] = Op::mma(qf, sf, dk[dt]);
-    }
+    dv_dk_step<T>(dv, Os, pf, dk, Qs, sf, qs + g * 4, qs + 16 + g * 4);
   }
-  if (kok) {
-    T* row = dqkv + ((long)b * L + key) * 3 * H * HD + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-      store4<T>(row + (long)H * HD + dt * 16 + g * 4, dk[dt][0] * scale, dk[dt][1] * scale,
-                dk[dt][2] * scale, dk[dt][3] * scale);
-      store4<T>(row + 2L * H * HD + dt * 16 + g * 4, dv[dt][0], dv[dt][1], dv[dt][2],
-                dv[dt][3]);
-    }
-  }
-}
-
-static size_t smem16(int L, int nw) {
-  const size_t LP = (L + 31) & ~31;
-  return LP * (LDR + LDT) * 2 + (LP + (size_t)nw * 16 * LDP) * sizeof(float);
+  if (kok) store_dk_dv<T>(dqkv + ((long)b * L + key) * 3 * H * HD + h * HD, H, g, dk, dv, scale);
 }
 
 // queries per forward block: 128 (8 waves) halves the K/V staging per query and doubles the
@@ -1092,8 +1114,7 @@ static int fwd16_nw() { return knobs().attn_fwd_nw == 4 ? 4 : 8; }
 // the flash-style forward's block: 8 waves (128 queries); MMDX_ATTN_FWD_NW = 4 | 16 selects
 // 64 / 256 (16 waves = one block per ViT head, K and V staged once instead of twice: C5
 // 2631 / 2640 vs 2653 / 2664 samples/s with 8, paired, tools/lab_attnnw.sh)
-static int fwd16_lse_nw(int L) {
-  (void)L;
+static int fwd16_lse_nw() {
   const int v = knobs().attn_fwd_nw;
   return v == 4 || v == 16 ? v : 8;
 }
@@ -1101,19 +1122,26 @@ static int bwd16_nw() {   // the same for the dQ kernel; MMDX_ATTN_BWD_NW=4 sele
   return knobs().attn_bwd_nw == 4 ? 4 : 8;
 }
 
-template <typename T>
 static size_t fwd_smem(int L) {
-  constexpr int NW = AttnCfg<T>::NW, QB = NW * 16, PAD = Vec16<T>::N;
-  const int LP = (L + 31) & ~31;  // multiple of the bf16 MFMA K (32)
+  constexpr int QB = NW32 * 16, PAD = Vec16<float>::N;
+  const int LP = attn_lp(L);
   const size_t kp = std::max((size_t)LP * (HD + PAD), (size_t)QB * (LP + PAD));
-  return sizeof(T) * (kp + (size_t)HD * (LP + PAD) + (size_t)QB * (HD + PAD));
+  return sizeof(float) * (kp + (size_t)HD * (LP + PAD) + (size_t)QB * (HD + PAD));
+}
+
+// One launch of a 16-bit kernel: nw waves per block, one block per 16 * nw rows of every
+// (batch, head), lds_bytes of dynamic LDS from the kernel's layout.
+template <typename K, typename... Args>
+static void launch16(K kern, int nw, size_t lds_bytes, int B, int L, int H, hipStream_t st,
+                     Args... args) {
+  mmdx_lds_max_once((const void*)kern);
+  hipLaunchKernelGGL(kern, dim3(blocks_per_head(L, nw) * H * B), dim3(nw * 64), lds_bytes, st,
+                     args...);
 }
 
 }  // namespace mmdx
 
 using namespace mmdx;
-
-__global__ void attn_counter_incr_kernel(uint64_t* c) { c[0] += 1; }
 
 extern "C" int mmdx_attention_fwd_ex(int dtype, const void* qkv, const int64_t* mask,
                                      const float* bias, int causal, int B, int L, int H,
@@ -1127,29 +1155,23 @@ extern "C" int mmdx_attention_fwd_ex(int dtype, const void* qkv, const int64_t* 
   hipStream_t st = (hipStream_t)stream;
   MMDX_DISPATCH(dtype, {
     if constexpr (std::is_same<T, float>::value) {
-      constexpr int QB = AttnCfg<T>::NW * 16;
-      const size_t sm = fwd_smem<T>(L);
+      const size_t sm = fwd_smem(L);
       MMDX_CHECK_ARG(sm <= 160 * 1024, "attention: L=%d needs %zu B LDS", L, sm);
-      mmdx_lds_max_once((const void*)attn_fwd_kernel<T>);
-      hipLaunchKernelGGL(attn_fwd_kernel<T>, dim3((L + QB - 1) / QB, H, B),
-                         dim3(AttnCfg<T>::NW * 64), sm, st, (const T*)qkv, mask, bias, causal,
-                         L, H, scale, p_drop, seed, (const uint64_t*)counter, (T*)out, probs);
+      mmdx_lds_max_once((const void*)attn_fwd_kernel);
+      hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks_per_head(L, NW32), H, B), dim3(NW32 * 64),
+                         sm, st, (const float*)qkv, mask, bias, causal, L, H, scale, p_drop, seed,
+                         (const uint64_t*)counter, (float*)out, probs);
     } else {
       auto launch = [&](auto kern, int nw) {
-        const size_t sm = smem16(L, nw);
-        mmdx_lds_max_once((const void*)kern);
-        const int qb = nw * 16;
-        hipLaunchKernelGGL(kern, dim3((L + qb - 1) / qb * H * B), dim3(nw * 64), sm, st,
-                           (const T*)qkv, mask, bias, causal, L, H, scale, p_drop, seed,
-                           (const uint64_t*)counter, (T*)out, probs, (float*)nullptr,
-                           (uint64_t*)nullptr);
+        launch16(kern, nw, QBlockLds(L, nw, sizeof(T)).bytes(true), B, L, H, st, (const T*)qkv,
+                 mask, bias, causal, L, H, scale, p_drop, seed, (const uint64_t*)counter, (T*)out,
+                 probs, (float*)nullptr, (uint64_t*)nullptr);
       };
       if (fwd16_nw() == 8) launch(attn_fwd16_kernel<T, 8>, 8);
       else launch(attn_fwd16_kernel<T, 4>, 4);
     }
   });
-  if (p_drop > 0.f && counter)
-    hipLaunchKernelGGL(attn_counter_incr_kernel, dim3(1), dim3(1), 0, st, counter);
+  if (p_drop > 0.f && counter) dropout_counter_advance(counter, st);
   MMDX_LAUNCH_CHECK();
   return 0;
 }
@@ -1162,8 +1184,7 @@ extern "C" int mmdx_attention_fwd(int dtype, const void* qkv, const int64_t* mas
 }
 
 extern "C" size_t mmdx_attention_workspace_size(int dtype, int B, int L, int H) {
-  const int LP = (L + 31) & ~31;  // multiple of the bf16 MFMA K (32)
-  return (size_t)B * H * L * LP * (dtype == F32 ? 4 : 2);
+  return (size_t)B * H * L * attn_lp(L) * (dtype == F32 ? 4 : 2);
 }
 
 extern "C" int mmdx_attention_bwd(int dtype, const void* qkv, const float* probs,
@@ -1178,37 +1199,26 @@ extern "C" int mmdx_attention_bwd(int dtype, const void* qkv, const float* probs
                  "attention bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   MMDX_DISPATCH(dtype, {
-    constexpr int QB = AttnCfg<T>::NW * 16;
     if constexpr (std::is_same<T, float>::value) {
-      const size_t sm = fwd_smem<T>(L);
+      const size_t sm = fwd_smem(L);
       MMDX_CHECK_ARG(sm <= 160 * 1024, "attention bwd: L=%d needs %zu B LDS", L, sm);
-      mmdx_lds_max_once((const void*)attn_bwd_q_kernel<T>);
-      hipLaunchKernelGGL(attn_bwd_q_kernel<T>, dim3((L + QB - 1) / QB, H, B),
-                         dim3(AttnCfg<T>::NW * 64), sm, st, (const T*)qkv, probs,
-                         (const T*)dout, L, H, scale, keep_scale, (T*)ws, (T*)dqkv);
+      mmdx_lds_max_once((const void*)attn_bwd_q_kernel);
+      hipLaunchKernelGGL(attn_bwd_q_kernel, dim3(blocks_per_head(L, NW32), H, B),
+                         dim3(NW32 * 64), sm, st, (const float*)qkv, probs, (const float*)dout, L,
+                         H, scale, keep_scale, (float*)ws, (float*)dqkv);
+      hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3(blocks_per_head(L, NW32) * H * B),
+                         dim3(NW32 * 64), 0, st, (const float*)qkv, probs, (const float*)dout,
+                         (const float*)ws, L, H, scale, keep_scale, (float*)dqkv);
     } else {
-      auto launch = [&](auto kern, int nw) {
-        const size_t sm = smem16(L, nw);
-        mmdx_lds_max_once((const void*)kern);
-        const int qb = nw * 16;
-        hipLaunchKernelGGL(kern, dim3((L + qb - 1) / qb * H * B), dim3(nw * 64), sm, st,
-                           (const T*)qkv, probs, (const T*)dout, L, H, scale, keep_scale,
-                           (T*)ws, (T*)dqkv);
+      auto launch_q = [&](auto kern, int nw) {
+        launch16(kern, nw, QBlockLds(L, nw, sizeof(T)).bytes(true), B, L, H, st, (const T*)qkv,
+                 probs, (const T*)dout, L, H, scale, keep_scale, (T*)ws, (T*)dqkv);
       };
-      if (bwd16_nw() == 8) launch(attn_bwd_q16_kernel<T, 8>, 8);
-      else launch(attn_bwd_q16_kernel<T, 4>, 4);
-    }
-    if constexpr (std::is_same<T, float>::value) {
-      hipLaunchKernelGGL(attn_bwd_kv_kernel<T>, dim3((L + QB - 1) / QB * H * B),
-                         dim3(AttnCfg<T>::NW * 64), 0, st, (const T*)qkv, probs,
-                         (const T*)dout, (const T*)ws, L, H, scale, keep_scale, (T*)dqkv);
-    } else {
-      const size_t sm = (size_t)((L + 31) & ~31) * LDT * 2 * sizeof(T);
-      auto kv16 = attn_bwd_kv16_kernel<T, 8>;
-      mmdx_lds_max_once((const void*)kv16);
-      hipLaunchKernelGGL(kv16, dim3((L + 127) / 128 * H * B), dim3(512),
-                         sm, st, (const T*)qkv, probs, (const T*)dout, (const T*)ws, L, H,
-                         scale, keep_scale, (T*)dqkv);
+      if (bwd16_nw() == 8) launch_q(attn_bwd_q16_kernel<T, 8>, 8);
+      else launch_q(attn_bwd_q16_kernel<T, 4>, 4);
+      launch16(attn_bwd_kv16_kernel<T, 8>, 8, KBlockLds(L, sizeof(T)).bytes(false), B, L, H, st,
+               (const T*)qkv, probs, (const T*)dout, (const T*)ws, L, H, scale, keep_scale,
+               (T*)dqkv);
     }
   });
   MMDX_LAUNCH_CHECK();
@@ -1227,23 +1237,17 @@ extern "C" int mmdx_attention_fwd_lse(int dtype, const void* qkv, const int64_t*
   MMDX_DISPATCH(dtype, {
     if constexpr (!std::is_same<T, float>::value) {
       auto launch = [&](auto kern, int nw) {
-        // (no probability tiles to transpose: the K / V images and the key mask only)
-        const size_t LP = (L + 31) & ~31;
-        const size_t sm = LP * (LDR + LDT) * sizeof(T) + LP * sizeof(float);
-        mmdx_lds_max_once((const void*)kern);
-        const int qb = nw * 16;
-        hipLaunchKernelGGL(kern, dim3((L + qb - 1) / qb * H * B), dim3(nw * 64), sm, st,
-                           (const T*)qkv, mask, (const float*)nullptr, 0, L, H, scale, p_drop,
-                           seed, (const uint64_t*)counter, (T*)out, (float*)nullptr, lse, rng);
+        launch16(kern, nw, QBlockLds(L, nw, sizeof(T)).bytes(false), B, L, H, st, (const T*)qkv,
+                 mask, (const float*)nullptr, 0, L, H, scale, p_drop, seed,
+                 (const uint64_t*)counter, (T*)out, (float*)nullptr, lse, rng);
       };
-      const int nw = fwd16_lse_nw(L);
+      const int nw = fwd16_lse_nw();
       if (nw == 16) launch(attn_fwd16_kernel<T, 16>, 16);
       else if (nw == 8) launch(attn_fwd16_kernel<T, 8>, 8);
       else launch(attn_fwd16_kernel<T, 4>, 4);
     }
   });
-  if (p_drop > 0.f && counter)
-    hipLaunchKernelGGL(attn_counter_incr_kernel, dim3(1), dim3(1), 0, st, counter);
+  if (p_drop > 0.f && counter) dropout_counter_advance(counter, st);
   MMDX_LAUNCH_CHECK();
   return 0;
 }
@@ -1265,21 +1269,14 @@ extern "C" int mmdx_attention_bwd_lse(int dtype, const void* qkv, const void* ou
   MMDX_CHECK_ARG(ws && ws_bytes >= mmdx_attention_lse_workspace_size(dtype, B, L, H),
                  "attention bwd (lse): workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int LP = (L + 31) & ~31;
   MMDX_DISPATCH(dtype, {
     if constexpr (!std::is_same<T, float>::value) {
-      const size_t sma = (size_t)LP * (LDR + LDT) * sizeof(T) + (size_t)LP * sizeof(float);
-      auto qk = attn_bwd_q16_lse_kernel<T, 8>;
-      mmdx_lds_max_once((const void*)qk);
-      hipLaunchKernelGGL(qk, dim3((L + 127) / 128 * H * B), dim3(512), sma, st, (const T*)qkv,
-                         (const T*)out, lse, rng, (const T*)dout, mask, L, H, scale, p_drop,
-                         (float*)ws, (T*)dqkv);
-      const size_t smb = (size_t)LP * LDT * 2 * sizeof(T) + (size_t)LP * 2 * sizeof(float);
-      auto kv = attn_bwd_kv16_lse_kernel<T, 8>;
-      mmdx_lds_max_once((const void*)kv);
-      hipLaunchKernelGGL(kv, dim3((L + 127) / 128 * H * B), dim3(512), smb, st, (const T*)qkv,
-                         lse, rng, (const T*)dout, mask, (const float*)ws, L, H, scale, p_drop,
-                         (T*)dqkv);
+      launch16(attn_bwd_q16_lse_kernel<T, 8>, 8, QBlockLds(L, 8, sizeof(T)).bytes(false), B, L, H,
+               st, (const T*)qkv, (const T*)out, lse, rng, (const T*)dout, mask, L, H, scale,
+               p_drop, (float*)ws, (T*)dqkv);
+      launch16(attn_bwd_kv16_lse_kernel<T, 8>, 8, KBlockLds(L, sizeof(T)).bytes(true), B, L, H, st,
+               (const T*)qkv, lse, rng, (const T*)dout, mask, (const float*)ws, L, H, scale,
+               p_drop, (T*)dqkv);
     }
   });
   MMDX_LAUNCH_CHECK();

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dropout_rng.h"
 #include "pool.h"
 #include "../../include/mmdx.h"
 
@@ -362,27 +363,22 @@ __global__ __launch_bounds__(256) void bias_grad_finalize_kernel(const float* __
 }
 
 // ----------------------------------------------------------------------------- dropout
-__device__ __forceinline__ uint32_t hash64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return (uint32_t)x;
-}
 template <typename T>
 __global__ void dropout_fwd_kernel(const T* __restrict__ x, long n, float p, uint64_t seed,
                                    uint64_t off, const uint64_t* __restrict__ ctr,
                                    T* __restrict__ y, uint8_t* __restrict__ mask) {
   const float scale = 1.f / (1.f - p);
-  if (ctr) off += ctr[0] << 32;
+  const uint64_t base = dropout_stream_base(seed, ctr) + off;
   GRID_STRIDE(i, n) {
-    const float u = (hash64(seed * 0x9E3779B97F4A7C15ULL + off + (uint64_t)i) >> 8) *
-                    (1.f / 16777216.f);
-    const uint8_t keep = u >= p;
+    const uint8_t keep = dropout_keep(base, (uint64_t)i, p);
     mask[i] = keep;
     y[i] = from_f<T>(keep ? to_f(x[i]) * scale : 0.f);
   }
 }
 __global__ void counter_incr_kernel(uint64_t* c) { c[0] += 1; }
+void dropout_counter_advance(uint64_t* counter, hipStream_t stream) {
+  hipLaunchKernelGGL(counter_incr_kernel, dim3(1), dim3(1), 0, stream, counter);
+}
 
 template <typename T>
 __global__ void dropout_bwd_kernel(const T* __restrict__ dy, const uint8_t* __restrict__ mask,
@@ -609,8 +605,7 @@ extern "C" int mmdx_dropout_fwd(int dtype, const void* x, long n, float p, uint6
   DISPATCH_T(dtype, hipLaunchKernelGGL(dropout_fwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0,
                                        (hipStream_t)stream, (const T*)x, n, p, seed, offset,
                                        (const uint64_t*)counter, (T*)y, mask));
-  if (counter)
-    hipLaunchKernelGGL(counter_incr_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, counter);
+  if (counter) dropout_counter_advance(counter, (hipStream_t)stream);
   MMDX_LAUNCH_CHECK();
   return 0;
 }

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dropout_rng.h"
 #include "pool.h"
 #include "../../include/mmdx.h"
 
@@ -859,19 +860,10 @@ static int bn_bwd_pair_t(int train, const void* dy, const uint8_t* mask, long ro
 constexpr int LN_MAXV = 4;
 
 // Dropout on the x input (DROP; BertSelfOutput / BertOutput: LayerNorm(dropout(dense) + res)):
-// element e = row * D + c of x is kept when hash(base + e) >= p, base = seed * phi +
-// (counter << 32) as mmdx_dropout_fwd draws it, and the kept value is rounded to T after the
+// element e = row * D + c of x is kept when dropout_keep(base, e, p) (dropout_rng.h), the
+// stream mmdx_dropout_fwd draws from, and the kept value is rounded to T after the
 // 1 / (1 - p) scale as that kernel stores it — so the normalised rows are bit-identical to
 // mmdx_dropout_fwd followed by mmdx_layernorm_fwd, without the dropped tensor or its mask.
-__device__ __forceinline__ uint32_t ln_drop_hash(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return (uint32_t)x;
-}
-__device__ __forceinline__ bool ln_keep(uint64_t base, long e, float p) {
-  return (ln_drop_hash(base + (uint64_t)e) >> 8) * (1.f / 16777216.f) >= p;
-}
 
 template <typename T, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x,
@@ -890,7 +882,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x,
   uint64_t dbase = 0;
   float dscale = 1.f;
   if constexpr (DROP) {
-    dbase = seed * 0x9E3779B97F4A7C15ULL + (ctr ? ctr[0] << 32 : 0ull);
+    dbase = dropout_stream_base(seed, ctr);
     dscale = 1.f / (1.f - p);
     if (rng_out && blockIdx.x == 0 && threadIdx.x == 0) rng_out[0] = dbase;
   }
@@ -909,7 +901,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x,
       for (int j = 0; j < VEC; ++j) {
         float av = to_f(a[j]);
         if constexpr (DROP)
-          av = to_f(from_f<T>(ln_keep(dbase, row * D + vi * VEC + j, p) ? av * dscale : 0.f));
+          av = to_f(
+              from_f<T>(dropout_keep(dbase, row * D + vi * VEC + j, p) ? av * dscale : 0.f));
         v[i][j] = av + (res ? to_f(b[j]) : 0.f);
         s += v[i][j];
       }
@@ -1065,7 +1058,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ xs,
           V od;
 #pragma unroll
           for (int j = 0; j < VEC; ++j)
-            od[j] = from_f<T>(ln_keep(dbase, row * D + vi * VEC + j, p) ? to_f(o[j]) * dscale
+            od[j] = from_f<T>(dropout_keep(dbase, row * D + vi * VEC + j, p) ? to_f(o[j]) * dscale
                                                                          : 0.f);
           *(V*)(dx_drop + row * D + vi * VEC) = od;
         }
@@ -1333,8 +1326,6 @@ extern "C" int mmdx_layernorm_fwd(int dtype, const void* x, const void* residual
   return 0;
 }
 
-__global__ void ln_counter_incr_kernel(uint64_t* c) { c[0] += 1; }
-
 extern "C" int mmdx_layernorm_fwd_dropout(int dtype, const void* x, const void* residual,
                                           long rows, int D, const float* gamma,
                                           const float* beta, float eps, float p, uint64_t seed,
@@ -1351,8 +1342,7 @@ extern "C" int mmdx_layernorm_fwd_dropout(int dtype, const void* x, const void* 
                                           st, (const T*)x, (const T*)residual, rows, D, gamma,
                                           beta, eps, (T*)y, (T*)sum_out, save_mean, save_rstd, p,
                                           seed, (const uint64_t*)counter, rng));
-  if (counter)
-    hipLaunchKernelGGL(ln_counter_incr_kernel, dim3(1), dim3(1), 0, st, counter);
+  if (counter) dropout_counter_advance(counter, st);
   MMDX_LAUNCH_CHECK();
   return 0;
 }

@@ -16,6 +16,7 @@
 #include <climits>
 
 #include "common.h"
+#include "dropout_rng.h"
 #include "../../include/mmdx.h"
 
 namespace mmdx {
@@ -204,12 +205,6 @@ __global__ __launch_bounds__(256) void t5_pos_bias_bwd_kernel(
 // q: [B][Lq] rows of ld_q elements (head h at +h*64); kv: [B][Lk][2][H][64] (k | v);
 // probs [B][H][Lq][Lk] fp32 with the dropout keep bit in the sign (as mmdx_attention_fwd).
 constexpr int XA_MAXK = 16;
-__device__ __forceinline__ uint32_t xa_hash64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return (uint32_t)x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void xattn_fwd_kernel(
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(
   const float inv = 1.f / sum;
   const bool drop = p_drop > 0.f;
   const float keep_scale = drop ? 1.f / (1.f - p_drop) : 1.f;
-  const uint64_t rbase = drop ? seed * 0x9E3779B97F4A7C15ULL + (ctr ? ctr[0] << 32 : 0ull) : 0ull;
+  const uint64_t rbase = drop ? dropout_stream_base(seed, ctr) : 0ull;
   float o[64];
 #pragma unroll
   for (int d = 0; d < 64; ++d) o[d] = 0.f;
@@ -253,7 +248,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(
     bool keep = true;
     if (drop) {
       const uint64_t idx = (((uint64_t)b * H + h) * Lq + qi) * (uint64_t)Lk + j;
-      keep = (xa_hash64(rbase + idx) >> 8) * (1.f / 16777216.f) >= p_drop;
+      keep = dropout_keep(rbase, idx, p_drop);
     }
     if (pr) pr[j] = keep ? p : -p;
     const float pe = keep ? p * keep_scale : 0.f;
@@ -663,8 +658,6 @@ extern "C" int mmdx_t5_position_bias_bwd(int dtype, const void* dscores, int B, 
   return 0;
 }
 
-__global__ void xattn_counter_incr_kernel(uint64_t* c) { c[0] += 1; }
-
 extern "C" int mmdx_xattn_fwd(int dtype, const void* q, long ldq, const void* kv, int B, int Lq,
                               int Lk, int H, float scale, float p_drop, uint64_t seed,
                               uint64_t* counter, void* out, float* probs, void* stream) {
@@ -678,8 +671,7 @@ extern "C" int mmdx_xattn_fwd(int dtype, const void* q, long ldq, const void* kv
                                         0, st, (const T*)q, ldq, (const T*)kv, B, Lq, Lk, H,
                                         scale, p_drop, seed, (const uint64_t*)counter, (T*)out,
                                         probs));
-  if (p_drop > 0.f && counter)
-    hipLaunchKernelGGL(xattn_counter_incr_kernel, dim3(1), dim3(1), 0, st, counter);
+  if (p_drop > 0.f && counter) dropout_counter_advance(counter, st);
   MMDX_LAUNCH_CHECK();
   return 0;
 }

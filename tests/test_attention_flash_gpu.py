@@ -121,6 +121,31 @@ def _err(got, ref, i):
     return (got - ref).abs().max().item() / den
 
 
+_DEFAULT_OUT = {}   # forward outputs at the default block sizes, one run per case
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,Ls,H", [(3, 37, 2), (4, 129, 6), (1, 256, 1)])
+@pytest.mark.parametrize("pd", [0.0, 0.1])
+@pytest.mark.parametrize("knob,nw", [("MMDX_ATTN_FWD_NW", 4), ("MMDX_ATTN_FWD_NW", 16),
+                                     ("MMDX_ATTN_BWD_NW", 4)])
+def test_flash_attention_block_sizes(dev, knobs, monkeypatch, dt, B, Ls, H, pd, knob, nw):
+    """The 4- and 16-wave instantiations the knobs select pass test_flash_attention's own
+    assertions, and the block size does not change the forward output by a bit.  The cases are
+    the smallest at which block and wave edges differ between the sizes: L % 4 != 0 in one
+    partial block; one query past a 128-row block (4 waves: three blocks, the last with one
+    live wave; 8: two blocks; 16: one block with seven idle waves); the full 16 key tiles."""
+    case = (dt, B, Ls, H, pd)
+    if case not in _DEFAULT_OUT:
+        _DEFAULT_OUT[case] = _run(dev, dt, B, Ls, H, True, pd)["out1"].clone()
+    knobs(knob, nw)
+    run, seen = _run, {}
+    # test_flash_attention's one call of _run, with its result kept for the comparison below
+    monkeypatch.setitem(globals(), "_run", lambda *a, **kw: seen.setdefault("r", run(*a, **kw)))
+    test_flash_attention(dev, dt, B, Ls, H, True, pd)
+    assert torch.equal(seen["r"]["out1"], _DEFAULT_OUT[case]), "output depends on block size"
+
+
 def test_flash_attention_vit_bert_shapes(dev):
     """The benched C5 geometries (ViT-B/16 L 197, BERT-base L 128 with dropout 0.1, 12
     heads, fp16) at a reduced batch."""
