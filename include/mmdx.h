@@ -852,6 +852,52 @@ int mmdx_reliability_bins(const float* logits, const float* target, int N, int C
                           const float* scale, const float* bias, const float* edges, int n_bins,
                           int64_t* out, void* stream);
 
+/* ---------------------------------------------------------------- bootstrap
+ * Non-parametric bootstrap over ROWS for the validation metrics: a row is resampled with all of
+ * its C labels.  Integer arithmetic with one owner per output: bit-reproducible and exactly
+ * comparable with a CPU reference (mmdx/bootstrap.py: reference_weights, reference_counts).
+ *
+ * mmdx_bootstrap_weights: w int32 [R][N]; w[r][i] = how often row i is drawn among the N draws
+ * of replicate r0 + r, so every row of w sums to N.  Draw k of replicate r is
+ *   idx = mulhi64(mix64(mix64(seed ^ ((r + 1) G)) + (k + 1) G), N),  G = 0x9E3779B97F4A7C15,
+ * mix64 the SplitMix64 output function (csrc/bootstrap_rng.h): it depends on (seed, r, k, N)
+ * alone, so batching with r0 is invisible.  N <= 131072: a block per replicate and window of
+ * 16384 rows makes all N draws and keeps the histogram of its window in LDS, plain stores; longer
+ * rows: integer atomics on w, which the entry point zeroes.
+ * Limits: R, N >= 1, r0 >= 0, R * N <= 2^26.
+ *
+ * mmdx_bootstrap_counts: out int64 [R][(C + 1)][5] = {u2, w_pos, w_neg, tp, fp}; row c < C is
+ * class c, row C the flattened (micro) problem in which element (i, c) carries w[r][i]:
+ *   w_pos / w_neg = sum of w[r][i] over the live positives / negatives,
+ *   u2 = sum over live (positive i, negative j) of w[r][i] w[r][j] ([s_i > s_j] + [s_i >= s_j])
+ *        (mmdx_auroc_pairs' u2 with multiplicities; AUROC = u2 / (2 w_pos w_neg)),
+ *   tp / fp = sum of w[r][i] over the live positives / negatives whose PRED flag is set.
+ * The score order does not depend on the replicate, so the caller sorts ONCE and passes items:
+ * an item is (row << 3) | flags, flags = 1 positive | 2 live (score not NaN) | 4 predicted; an
+ * item that is not live counts nowhere, and every item's row is < N.
+ *   class_items int32 [2][C][n_pad], n_pad = N rounded up to a multiple of 4: column c in
+ *     ascending score order, within equal scores positives first ([0]: order A) or negatives
+ *     first ([1]: order B); the pad items are 0;
+ *   micro_items int32 [2][m_pad], m_pad = N * C rounded up likewise: all N * C elements.
+ * With T(order) = sum over positives k of w_k * (negative weight strictly earlier in the order),
+ * u2 = T(A) + T(B): a weighted exclusive prefix scan, no tie logic.  Three launches: the weights
+ * are transposed to [N][R rounded up to 8] (the 8 replicate weights of a row then share 32
+ * contiguous bytes); a block scans one 2048-item segment of one column in one order for 8
+ * replicates and stores the segment's partial sums; then one thread per (replicate, column) adds
+ * the segments in order with their cross terms and writes the output row.  Plain stores
+ * throughout: no atomics, no memset.  workspace: mmdx_bootstrap_counts_workspace_size(R, N, C)
+ * bytes (0 for illegal R, N, C; the transposed weights plus 48 bytes per replicate and segment),
+ * 16-byte aligned, no initialisation needed.
+ * weights int32 [R][N], non-negative, every row summing to at most 2^31 / C (a bootstrap row sums
+ * to N): the prefix sums are 32-bit, the products 64-bit (u2 <= 2^49).  Neither is checked.
+ * Limits (argument errors): 1 <= C <= 64, N * C <= 2^24, R * N <= 2^26, item arrays 16-byte
+ * aligned, a short or misaligned workspace. */
+int mmdx_bootstrap_weights(int R, long r0, int N, uint64_t seed, int* w, void* stream);
+size_t mmdx_bootstrap_counts_workspace_size(int R, int N, int C);
+int mmdx_bootstrap_counts(const int* class_items, const int* micro_items, const int* weights,
+                          int R, int N, int C, int64_t* out, void* workspace, size_t ws_bytes,
+                          void* stream);
+
 /* ---------------------------------------------------------------- Grad-CAM
  * Heatmaps of the disease head at the trunk's last conv stage.  Between that feature map and
  * the logits there is only the global average pool and the heads, so the Grad-CAM channel

@@ -14,5 +14,6 @@ from .amp import GradScaler  # noqa: F401
 from .preprocess import preprocess_batch  # noqa: F401
 from .augment import Augment  # noqa: F401
 from .losses import DiseaseLoss  # noqa: F401
+from . import bootstrap  # noqa: F401
 
 __version__ = "0.1.0"

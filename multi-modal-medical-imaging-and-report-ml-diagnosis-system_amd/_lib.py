@@ -219,6 +219,9 @@ SIGNATURES = {
     "mmdx_calib_fit_step": (i32, [vp, vp, i64, i32, vp, i32, i32, i32, i32, i64, f64, vp, vp, vp,
                                   vp, vp, sz, vp]),
     "mmdx_reliability_bins": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
+    "mmdx_bootstrap_weights": (i32, [i32, i64, i32, u64, vp, vp]),
+    "mmdx_bootstrap_counts_workspace_size": (sz, [i32, i32, i32]),
+    "mmdx_bootstrap_counts": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),
     "mmdx_cam_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mmdx_augment_affine": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),

@@ -687,6 +687,115 @@ def reliability_bins(logits, target, scale=None, bias=None, n_bins=15):
     return out[:(C + 1) * n_bins * 4].view(C + 1, n_bins, 4), out[(C + 1) * n_bins * 4:]
 
 
+# ----------------------------------------------------------------------------- bootstrap
+def bootstrap_weights(R, N, seed, r0=0, device=None):
+    """int32 [R, N] on `device`: the resampling weights of bootstrap replicates r0 ... r0 + R - 1
+    (mmdx_bootstrap_weights; mmdx.bootstrap.reference_weights is the numpy statement).  Every
+    row sums to N.  Draw k of replicate r depends on (seed, r, k, N) alone, so a run split into
+    batches with r0 equals the unsplit one.  Bit-reproducible.  R * N <= 2^26."""
+    from .bootstrap import MAX_WEIGHTS
+    for what, v in (("R", R), ("N", N), ("seed", seed), ("r0", r0)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"bootstrap_weights: {what} must be an int, got {type(v).__name__}")
+    if R < 1 or N < 1 or r0 < 0 or R * N > MAX_WEIGHTS or r0 + R >= 2 ** 62:
+        raise ValueError(f"bootstrap_weights: R = {R}, N = {N}, r0 = {r0} outside R, N >= 1, "
+                         "r0 >= 0, R * N <= 2^26")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ValueError(f"bootstrap_weights: device {device} is not a GPU (there is no CPU path)")
+    w = torch.empty((R, N), dtype=torch.int32, device=device)
+    with torch.cuda.device(w.device):
+        call("mmdx_bootstrap_weights", R, r0, N, seed & 0xFFFFFFFFFFFFFFFF, ptr(w), stream())
+    return w
+
+
+def _boot_items(key, flags, n_pad):
+    """int32 [2, cols, n_pad] from key fp32 / flags int32 [n, cols]: per column the items
+    (row << 3) | flags in ascending key order, positives first within ties ([0]) and negatives
+    first ([1]), zero-padded.  Two stable sorts each: by label, then by key."""
+    n, cols = key.shape
+    out = torch.zeros((2, cols, n_pad), dtype=torch.int32, device=key.device)
+    neg = 1 - (flags & 1)
+    for o, first in enumerate((neg, 1 - neg)):          # the label that goes first sorts as 0
+        p1 = torch.sort(first.to(torch.uint8), dim=0, stable=True)[1]
+        p2 = torch.sort(torch.gather(key, 0, p1), dim=0, stable=True)[1]
+        row = torch.gather(p1, 0, p2)
+        item = (row << 3) | torch.gather(flags, 0, row).to(torch.int64)
+        out[o, :, :n] = item.t().to(torch.int32)
+    return out
+
+
+def bootstrap_plan(scores, target, pred=None):
+    """Everything of the bootstrap that does not depend on the replicate: the sorted orders and
+    the per-element flags, from fp32 contiguous [N, C] scores and targets (positive iff > 0.5;
+    a NaN score drops the element) and an optional bool [N, C] `pred` (the elements predicted
+    positive, for tp / fp).  torch sorts and elementwise ops on the device, done once; no host
+    sync.  Returns an opaque tuple for bootstrap_counts.  1 <= C <= 64, N * C <= 2^24."""
+    from .bootstrap import MAX_CLASSES, MAX_ITEMS
+    N, C = _calib_inputs("bootstrap_plan", scores, target)
+    if N < 1 or C < 1 or C > MAX_CLASSES or N * C > MAX_ITEMS:
+        raise ValueError(f"bootstrap_plan: [N, C] = [{N}, {C}] outside 1 <= C <= {MAX_CLASSES}, "
+                         "1 <= N * C <= 2^24")
+    if pred is not None:
+        if not torch.is_tensor(pred) or pred.dtype != torch.bool:
+            raise TypeError("bootstrap_plan: pred must be a bool tensor")
+        if pred.shape != scores.shape or pred.device != scores.device:
+            raise ValueError(f"bootstrap_plan: pred {tuple(pred.shape)} on {pred.device} for "
+                             f"scores {tuple(scores.shape)} on {scores.device}")
+    flags = (target > 0.5).to(torch.int32) | ((~torch.isnan(scores)).to(torch.int32) << 1)
+    if pred is not None:
+        flags = flags | (pred.to(torch.int32) << 2)
+    key = scores + 0.0   # -0.0 becomes +0.0: the two tie under any sort
+    class_items = _boot_items(key, flags, (N + 3) & ~3)
+    # the micro column sorts all N * C elements; an element's weight row is element // C
+    m = N * C
+    micro = _boot_items(key.reshape(m, 1), flags.reshape(m, 1), (m + 3) & ~3)[:, 0]
+    e = micro >> 3
+    micro = torch.where(torch.arange(micro.shape[1], device=micro.device) < m,
+                        (torch.div(e, C, rounding_mode="floor") << 3) | (micro & 7),
+                        torch.zeros_like(micro))
+    return class_items, micro.contiguous(), N, C
+
+
+def bootstrap_counts(plan, weights, out=None):
+    """int64 [R, C + 1, 5] = (u2, w_pos, w_neg, tp, fp) per replicate and class, row C micro
+    (mmdx_bootstrap_counts; mmdx.bootstrap: the definition, reference_counts and intervals),
+    from a bootstrap_plan and non-negative contiguous int32 [R, N] weights on the plan's device
+    (bootstrap_weights, or any multiplicities whose rows sum to at most 2^31 / C; neither is
+    checked: that would be a host sync).  A weighted prefix scan over the plan's shared sort:
+    exact integers, bit-reproducible.  `out` (int64 contiguous [R, C + 1, 5]) is filled in
+    place when given.  R * N <= 2^26."""
+    from .bootstrap import MAX_WEIGHTS
+    try:
+        class_items, micro_items, N, C = plan
+    except (TypeError, ValueError):
+        raise TypeError("bootstrap_counts: plan must come from bootstrap_plan") from None
+    if not torch.is_tensor(weights) or weights.dtype != torch.int32:
+        raise TypeError("bootstrap_counts takes int32 weights")
+    if weights.dim() != 2 or weights.shape[1] != N or weights.shape[0] < 1:
+        raise ValueError(f"bootstrap_counts: weights {tuple(weights.shape)} for a plan of "
+                         f"{N} rows: [R, {N}] expected")
+    R = weights.shape[0]
+    if R * N > MAX_WEIGHTS:
+        raise ValueError(f"bootstrap_counts: R * N = {R * N} exceeds 2^26: split the replicates")
+    if weights.device != class_items.device:
+        raise ValueError(f"bootstrap_counts: weights on {weights.device}, the plan on "
+                         f"{class_items.device}")
+    if not weights.is_contiguous():
+        raise ValueError("bootstrap_counts: weights are not contiguous (never copied here)")
+    if out is None:
+        out = torch.empty((R, C + 1, 5), dtype=torch.int64, device=weights.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.int64 or out.shape != (R, C + 1, 5)
+          or out.device != weights.device or not out.is_contiguous()):
+        raise ValueError(f"bootstrap_counts: out must be contiguous int64 [{R}, {C + 1}, 5] on "
+                         f"{weights.device}")
+    n = L.lib().mmdx_bootstrap_counts_workspace_size(R, N, C)
+    ws = torch.empty(n, dtype=torch.uint8, device=weights.device)
+    call("mmdx_bootstrap_counts", ptr(class_items), ptr(micro_items), ptr(weights), R, N, C,
+         ptr(out), ptr(ws), n, stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- Grad-CAM
 def cam_raw(fmap, alpha):
     """raw[b, c, h, w] = relu(sum_k alpha[b, c, k] * fmap[b, h, w, k]), fp32 [B, C, H, W], from

@@ -8,7 +8,8 @@ function here, in float64 from exact integers, so it can be tested without a GPU
 - `pick_thresholds`: per-class F1-optimal probability thresholds from a threshold sweep;
 - `rouge_l`: token-id ROUGE-L F1 of generated reports;
 - `evaluate`: the loop that feeds them from held-out batches (and, with `calibrate`, fits and
-  measures a probability calibration: mmdx.calibration).
+  measures a probability calibration: mmdx.calibration; with `bootstrap`, adds row-bootstrap
+  confidence intervals: mmdx.bootstrap).
 
 `evaluate()` runs in ONE process: pair counts need every score on one rank, so data-parallel
 evaluation is out of scope (gather the logits to one rank first).  The AUROC kernel counts all
@@ -224,7 +225,8 @@ def _calibration_report(x, C, n_bins, ignored, mode):
 
 def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=None,
              grid_probs=None, generate=False, gen_kwargs=None, report_labels=None,
-             compute_dtype=None, criterion=None, calibrate=None, n_bins=15):
+             compute_dtype=None, criterion=None, calibrate=None, n_bins=15, bootstrap=0,
+             ci_level=0.95, bootstrap_seed=0):
     """Validation metrics of the three modules over `batches`, an iterable of
     (images, patient_details, labels) as data.LocalCXRBatches yields them.
 
@@ -263,6 +265,21 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     map fitted on the same rows are IN-SAMPLE: they show what the map can do, not what it will
     do on new data.
 
+    `bootstrap` = R > 0 (default 0: today's launches, copies, keys and bits) adds R bootstrap
+    replicates over ROWS (mmdx.bootstrap) after that copy.  The thresholds are picked on the host
+    as always, go back to the device, and stay FIXED: pred = (the swept logits >= the chosen
+    threshold's grid logit), so a replicate re-weights the confusion counts of the chosen grid
+    points but never re-picks a threshold.  The sort plan is built from the raw masked logits
+    (AUROC stays the uncalibrated number); the replicates run in batches of
+    mmdx.bootstrap.batch_size(R, n) (weights workspace <= 64 MiB) and all of them reach the host
+    in ONE further copy: two copies with bootstrap, one without.  The result gains "boot", the
+    int64 [R, C + 1, 5] array itself (for mmdx.bootstrap.paired_delta), and "ci": level,
+    n_replicates, seed, and an mmdx.bootstrap.intervals leaf {lo, hi, se, n_valid} for
+    val_auroc_micro, val_auroc_macro, each of val_auroc_per_class, val_f1_micro and, under
+    per_class, each class's sensitivity, specificity and f1 at its threshold.  `ci_level` is the
+    coverage, `bootstrap_seed` the stream (same seed and rows = same resamples, which is what
+    paired_delta needs).
+
     Returns n, val_loss, val_auroc_micro, val_auroc_macro, val_auroc_per_class, thresholds,
     val_f1_micro (at the chosen thresholds), val_f1_micro_at_0p5, per_class (precision, recall,
     f1, n_pos, ...) and, with generate, val_rougeL.  Single process only (module docstring)."""
@@ -272,6 +289,8 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     if tokenize is None:
         def tokenize(texts):
             return tokenize_patient_details(texts, max_len=96)
+    from . import bootstrap as B
+    n_boot, ci_level, bootstrap_seed = B.check_args(bootstrap, ci_level, bootstrap_seed)
     grid = sorted(set(float(p) for p in (grid_probs if grid_probs is not None
                                          else default_grid())) | {0.5})
     thr_host = grid_logits(grid)
@@ -383,6 +402,29 @@ def evaluate(image_encoder, text_encoder, fusion_model, batches, *, tokenize=Non
     if calibrate is not None:
         out["calibration"] = _calibration_report(
             host[(C + 1) * 4 + 2 * C * T + C:-1], C, n_bins, ign_h, cal_mode)
+    if n_boot:
+        if n * C > B.MAX_ITEMS:
+            raise ValueError(f"evaluate(bootstrap=...): n * C = {n * C} exceeds 2^24")
+        with torch.no_grad():
+            # the chosen thresholds as the sweep compared them: the grid's own fp32 logits
+            thr_c = torch.from_numpy(np.array([thr_host[grid.index(p)] for p in
+                                               picked["thresholds"]], np.float32)).to(z.device)
+            plan = F.bootstrap_plan(zm.contiguous(), ym.contiguous(), z_sweep >= thr_c)
+            boot = torch.empty((n_boot, C + 1, 5), dtype=torch.int64, device=z.device)
+            step = B.batch_size(n_boot, n)
+            for r0 in range(0, n_boot, step):
+                rb = min(step, n_boot - r0)
+                w = F.bootstrap_weights(rb, n, bootstrap_seed, r0=r0, device=z.device)
+                F.bootstrap_counts(plan, w, out=boot[r0:r0 + rb])
+            boot_h = boot.cpu().numpy()  # the second (and last) device-to-host copy
+        iv = B.intervals(boot_h, ci_level)
+        out["boot"] = boot_h
+        out["ci"] = {"level": ci_level, "n_replicates": n_boot, "seed": bootstrap_seed,
+                     "val_auroc_micro": iv["auroc_micro"], "val_auroc_macro": iv["auroc_macro"],
+                     "val_auroc_per_class": iv["auroc_per_class"],
+                     "val_f1_micro": iv["f1_micro"],
+                     "per_class": [{k: iv[f"{k}_per_class"][c] for k in
+                                    ("sensitivity", "specificity", "f1")} for c in range(C)]}
     if generate and has_head:
         width = max(g.shape[1] for g in gen_ids)
         pred = [row + [0] * (width - len(row)) for g in gen_ids for row in g.tolist()]

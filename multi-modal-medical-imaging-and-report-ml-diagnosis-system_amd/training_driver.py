@@ -153,7 +153,7 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
-                   augment=None, criterion=None, uncertain=None, calibrate=None):
+                   augment=None, criterion=None, uncertain=None, calibrate=None, bootstrap=0):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -182,7 +182,17 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     probability calibration on the held-out rows (evaluate(calibrate=...), so it needs
     val_rows > 0: ValueError otherwise), stores the map under artifacts["calibration"], where
     inference() finds it, and registers the in-sample val_ece_micro after calibration; the
-    stored thresholds then refer to the calibrated probabilities."""
+    stored thresholds then refer to the calibrated probabilities.
+
+    bootstrap (replicates, default 0 = no intervals) is passed to evaluate(bootstrap=...): row
+    bootstrap intervals of the held-out metrics (mmdx.bootstrap), so it needs val_rows > 0 too.
+    out["val"] then carries "ci" and "boot", and val_auroc_micro_ci_lo / _hi and
+    val_auroc_macro_ci_lo / _hi are registered next to the point values."""
+    from .bootstrap import check_args
+    bootstrap = check_args(bootstrap, who="training_tests")[0]
+    if bootstrap and val_rows <= 0:
+        raise ValueError("training_tests(bootstrap=...) resamples held-out rows: it needs "
+                         "val_rows > 0")
     if calibrate is not None:
         from .calibration import MODES
         if calibrate not in MODES:
@@ -376,7 +386,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                                        shuffle=False, device=dev,
                                        uncertain=None if uncertain is None else "ignore"),
                        generate=True, gen_kwargs=gen, report_labels=val_labels,
-                       criterion=None if plain_loss else criterion, calibrate=calibrate)
+                       criterion=None if plain_loss else criterion, calibrate=calibrate,
+                       bootstrap=bootstrap)
         out["val"] = val
         metrics = {k: (None if v != v else v) for k, v in
                    ((k, val[k]) for k in ("val_auroc_micro", "val_auroc_macro", "val_loss",
@@ -389,6 +400,16 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             metrics["val_ece_micro"] = None if ece != ece else ece
             log(f"[VAL] calibration {calibrate}: ece micro {cal['before']['val_ece_micro']:.4f}"
                 f" -> {ece:.4f} (in-sample), status {cal['status']}")
+        if bootstrap:
+            ci = val["ci"]
+            for k in ("val_auroc_micro", "val_auroc_macro"):
+                for end in ("lo", "hi"):
+                    v = ci[k][end]
+                    metrics[f"{k}_ci_{end}"] = None if v != v else v
+            log(f"[VAL] bootstrap {bootstrap} replicates, level {ci['level']}: auroc micro "
+                f"[{ci['val_auroc_micro']['lo']:.4f}, {ci['val_auroc_micro']['hi']:.4f}] macro "
+                f"[{ci['val_auroc_macro']['lo']:.4f}, {ci['val_auroc_macro']['hi']:.4f}] "
+                f"f1 micro [{ci['val_f1_micro']['lo']:.4f}, {ci['val_f1_micro']['hi']:.4f}]")
         log(f"[VAL] n={val['n']} loss={val['val_loss']:.4f} auroc micro="
             f"{val['val_auroc_micro']:.4f} macro={val['val_auroc_macro']:.4f} f1 micro="
             f"{val['val_f1_micro']:.4f} (at 0.5: {val['val_f1_micro_at_0p5']:.4f}) rougeL="
