@@ -939,6 +939,51 @@ int mmdx_augment_affine(const float* x, const float* params, int B, int C, int H
                         const float* mean, const float* stdv, int clamp, float* out,
                         void* stream);
 
+/* ---------------------------------------------------------------- CLAHE
+ * Contrast-limited adaptive histogram equalisation of 8-bit images (the algorithm of OpenCV's
+ * CLAHE_Impl; mmdx/clahe.py states it and its numpy `reference` is the definition these
+ * kernels equal byte for byte).  pixels: decoded HWC uint8 images packed back to back, the
+ * buffer mmdx_image_preprocess takes; one descriptor per image.  Each channel is an
+ * independent plane.
+ *
+ * mmdx_clahe_luts: per (image, channel, tile) the 256-bin histogram of the tile of the
+ * reflect-101 extended image, clipped at `clip` (0 = no clipping) with the excess redistributed
+ * (clipped / 256 to every bin, the remainder res to the bins i with i % step == 0 and
+ * i / step < res, step = max(256 / res, 1)), prefix-summed, and
+ * lut[i] = clamp(rint(float(cdf[i]) * lut_scale), 0, 255) written as 256 bytes at
+ * luts[lut_off + ((channel * tiles_y + tile row) * tiles_x + tile column) * 256].
+ *
+ * mmdx_clahe_apply: out of place into a buffer of the same packed layout.  Pixel (y, x) blends
+ * the LUTs of the tile rows max(y1, 0), min(y1 + 1, tiles_y - 1) and columns alike, where
+ * f = float(y) * (1.0f / tile_h) - 0.5f, y1 = floor(f), ya = f - y1, ya1 = 1.0f - ya:
+ * r = (L11 xa1 + L12 xa) ya1 + (L21 xa1 + L22 xa) ya, every operation a correctly-rounded fp32
+ * one (no fused multiply-add), out = clamp(rint(r), 0, 255).
+ *
+ * Both take the descriptor table twice: descs_host (HOST memory) is validated in full before
+ * any launch - geometry, limits, and every offset against pixel_bytes / lut_bytes / out_bytes -
+ * and sizes the grid; descs_dev is the same table in DEVICE memory, which the kernels read.
+ * Limits: c in {1, 3}; 1 <= tiles_x, tiles_y <= 16; w >= 2 tiles_x, h >= 2 tiles_y; w, h <=
+ * 65535; tile_w * tile_h <= 2^24; B <= 65535; lut_off a multiple of 256, LUTs and outputs in
+ * descriptor order without overlap; luts 4-byte aligned; out must not overlap pixels.
+ * No workspace; integer atomics in LDS only, so the result is bit-reproducible. */
+typedef struct {
+  long src_off, dst_off; /* byte offsets of the image's HWC pixels: source, destination */
+  long lut_off;          /* byte offset of the image's [c][tiles_y][tiles_x][256] LUTs */
+  int w, h, c;           /* width, height, channels (1 or 3) */
+  int tiles_x, tiles_y;  /* tiles per row, per column */
+  int tile_w, tile_h;    /* tile size of the extended image */
+  int clip;              /* histogram clip in counts, 0 = none */
+  float lut_scale;       /* 255.0f / (tile_w * tile_h) */
+} mmdx_clahe_desc;
+size_t mmdx_clahe_desc_size(void); /* sizeof(mmdx_clahe_desc): binding layout check */
+int mmdx_clahe_luts(const uint8_t* pixels, size_t pixel_bytes, const mmdx_clahe_desc* descs_host,
+                    const mmdx_clahe_desc* descs_dev, int B, uint8_t* luts, size_t lut_bytes,
+                    void* stream);
+int mmdx_clahe_apply(const uint8_t* pixels, size_t pixel_bytes,
+                     const mmdx_clahe_desc* descs_host, const mmdx_clahe_desc* descs_dev, int B,
+                     const uint8_t* luts, size_t lut_bytes, uint8_t* out, size_t out_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

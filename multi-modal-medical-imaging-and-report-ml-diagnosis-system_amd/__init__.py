@@ -13,6 +13,7 @@ from .optim import AdamW, clip_grad_norm_  # noqa: F401
 from .amp import GradScaler  # noqa: F401
 from .preprocess import preprocess_batch  # noqa: F401
 from .augment import Augment  # noqa: F401
+from .clahe import Clahe  # noqa: F401
 from .losses import DiseaseLoss  # noqa: F401
 from . import bootstrap  # noqa: F401
 

@@ -226,6 +226,9 @@ SIGNATURES = {
     "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mmdx_augment_affine": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),
                                   i32, vp, vp]),
+    "mmdx_clahe_desc_size": (sz, []),
+    "mmdx_clahe_luts": (i32, [vp, sz, vp, vp, i32, vp, sz, vp]),
+    "mmdx_clahe_apply": (i32, [vp, sz, vp, vp, i32, vp, sz, vp, sz, vp]),
 }
 
 _lib = None

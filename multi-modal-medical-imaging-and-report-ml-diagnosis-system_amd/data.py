@@ -199,10 +199,13 @@ class LocalCXRBatches:
     on the GPU after the transform; it draws from its own Generator, so the shuffle order is the
     one without it, and None yields the transform's output untouched.  `uncertain` is an
     apply_uncertain() policy for -1 labels, applied once here; None (default) yields the stored
-    label values bit for bit."""
+    label values bit for bit.  `clahe` (an mmdx.Clahe) equalises the decoded full-resolution
+    pixels on the GPU before the transform, hence before `augment`; it is part of the model's
+    input definition, so training and validation loaders of one model carry the same setting.
+    None yields the unequalised batches, bit for bit what they were without the argument."""
 
     def __init__(self, df, image_root, batch_size=32, shuffle=True, seed=0, drop_last=False,
-                 device=None, augment=None, uncertain=None):
+                 device=None, augment=None, uncertain=None, clahe=None):
         self.keys, self.labels = construct_input_label_pairs_for_image_encoder_dataset(df)
         if uncertain is not None and self.labels:
             self.labels = list(apply_uncertain(np.stack(self.labels), uncertain))
@@ -214,6 +217,12 @@ class LocalCXRBatches:
         self.drop_last = drop_last
         self.device = device
         self.augment = augment
+        if clahe is not None:
+            from .clahe import Clahe
+            if not isinstance(clahe, Clahe):
+                raise TypeError(f"clahe must be an mmdx.Clahe or None, got "
+                                f"{type(clahe).__name__}")
+        self.clahe = clahe
 
     def __len__(self):
         n = len(self.keys)
@@ -234,7 +243,7 @@ class LocalCXRBatches:
             if self.drop_last and len(idx) < self.batch_size:
                 break
             imgs = [open_image(self.image_root, self.keys[i]) for i in idx]
-            x = preprocess_batch(imgs, dev)
+            x = preprocess_batch(imgs, dev, clahe=self.clahe)
             if self.augment is not None:
                 x = self.augment(x)
             y = torch.from_numpy(np.stack([self.labels[i] for i in idx])).to(dev)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -17,7 +18,7 @@ from ._lib import call, ptr, stream
 __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
-    "augment_affine", "disease_loss", "calib_fit", "reliability_bins",
+    "augment_affine", "disease_loss", "calib_fit", "reliability_bins", "clahe",
 ]
 
 
@@ -878,3 +879,62 @@ def augment_affine(x, params, mean=None, std=None, clamp=True, out=None):
              (ctypes.c_float * C)(*m.tolist()), (ctypes.c_float * C)(*s.tolist()),
              int(bool(clamp)), ptr(out), stream())
     return out
+
+
+# ----------------------------------------------------------------------------- CLAHE
+def clahe_passes(px, descs, lut_bytes):
+    """The two CLAHE launches (mmdx_clahe_luts, mmdx_clahe_apply) on the packed device pixel
+    buffer `px` that the table `descs` of clahe.plan describes: returns (equalised buffer of
+    the same layout, LUT buffer).  The C entries validate the table against the buffers before
+    they launch; nothing here copies pixels or synchronises."""
+    from . import clahe as K
+    if px.dtype != torch.uint8 or px.dim() != 1 or not px.is_contiguous():
+        raise ValueError("clahe: the pixel buffer must be a flat contiguous uint8 tensor")
+    L.require_device(px)
+    if call("mmdx_clahe_desc_size") != K.DESC.itemsize:
+        raise RuntimeError("mmdx_clahe_desc layout differs between the library and clahe.DESC")
+    B, total = len(descs), px.numel()
+    with torch.cuda.device(px.device):
+        d_desc = torch.from_numpy(descs.view(np.uint8).copy()).to(px.device, non_blocking=True)
+        luts = torch.empty(lut_bytes, dtype=torch.uint8, device=px.device)
+        out = torch.empty_like(px)
+        call("mmdx_clahe_luts", ptr(px), total, descs.ctypes.data, ptr(d_desc), B, ptr(luts),
+             lut_bytes, stream())
+        call("mmdx_clahe_apply", ptr(px), total, descs.ctypes.data, ptr(d_desc), B, ptr(luts),
+             lut_bytes, ptr(out), total, stream())
+    return out, luts
+
+
+def clahe(images, clip_limit=2.0, tiles=(8, 8), return_luts=False, device=None):
+    """CLAHE (mmdx.clahe: the definition and its numpy `reference`, which this equals byte for
+    byte) of a list of HxW / HxWx{1,3} uint8 arrays or PIL L / RGB images of any sizes, in two
+    launches for the whole list.  Returns a list of device uint8 tensors of the inputs' shapes,
+    and with return_luts also a list of the uint8 LUTs, [ty, tx, 256] for an HxW input and
+    [C, ty, tx, 256] otherwise.  Limits (TypeError / ValueError before any launch): uint8 only,
+    C in {1, 3}, 1 <= tx, ty <= 16, W >= 2 tx, H >= 2 ty, tile area <= 2^24, sides <= 65535,
+    clip_limit finite."""
+    from . import clahe as K
+    setting = K.Clahe(clip_limit, tiles)
+    if isinstance(images, (np.ndarray, torch.Tensor)) or hasattr(images, "mode"):
+        raise TypeError("clahe takes a list of images")
+    shapes = [np.asarray(im).shape for im in images]
+    arrays = [K.as_planes(im) for im in images]
+    descs, total, lut_bytes = K.plan(arrays, setting)   # every limit, before any upload
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("functional.clahe runs on the GPU (HIP); mmdx.clahe.reference is "
+                           "the host statement")
+    host = np.concatenate([a.reshape(-1) for a in arrays])
+    with torch.cuda.device(device):
+        out, luts = clahe_passes(torch.from_numpy(host).to(device), descs, lut_bytes)
+    tx, ty = setting.tiles
+    res, tabs = [], []
+    for d, a, shp in zip(descs, arrays, shapes):
+        h, w, c = a.shape
+        o, lo = int(d["dst_off"]), int(d["lut_off"])
+        res.append(out[o:o + h * w * c].view(shp))
+        t = luts[lo:lo + c * ty * tx * 256].view(c, ty, tx, 256)
+        tabs.append(t[0] if len(shp) == 2 else t)
+    return (res, tabs) if return_luts else res

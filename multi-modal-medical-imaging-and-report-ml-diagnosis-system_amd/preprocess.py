@@ -159,9 +159,18 @@ def plan_batch(arrays):
     return descs, coef.astype(np.int32), max(temp_off, 1), max_trows, src_off
 
 
-def preprocess_batch(images, device=None) -> torch.Tensor:
+def preprocess_batch(images, device=None, clahe=None) -> torch.Tensor:
     """PIL images (L/RGB, any sizes) -> [B, 3, 224, 224] fp32 on the GPU, identical to
-    torch.stack([image_transfom_into_tensor(im) for im in images])."""
+    torch.stack([image_transfom_into_tensor(im) for im in images]).
+
+    clahe (an mmdx.Clahe, default None = the two launches and the bits above) equalises the
+    full-resolution pixels first: two more launches (mmdx.clahe) on the uploaded pixel buffer,
+    no further host-device copy of pixels and no further synchronisation.  The result is that
+    of transforming mmdx.clahe.reference(im, ...) of every image."""
+    if clahe is not None:
+        from . import clahe as K
+        if not isinstance(clahe, K.Clahe):
+            raise TypeError(f"clahe must be an mmdx.Clahe or None, got {type(clahe).__name__}")
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -172,6 +181,8 @@ def preprocess_batch(images, device=None) -> torch.Tensor:
     if not arrays:
         raise ValueError("empty batch")
     descs, coef, temp_bytes, max_trows, total = plan_batch(arrays)
+    if clahe is not None:  # its limits raise here, before anything is uploaded
+        cl_descs, _, cl_lut_bytes = K.plan(arrays, clahe)
     host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
     hv = host.numpy()
     off = 0
@@ -184,6 +195,9 @@ def preprocess_batch(images, device=None) -> torch.Tensor:
     temp = torch.empty(temp_bytes, dtype=torch.uint8, device=device)
     out = torch.empty((len(arrays), 3, CROP, CROP), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
+        if clahe is not None:  # same packed layout, same descriptors for the transform
+            from .functional import clahe_passes
+            px, _ = clahe_passes(px, cl_descs, cl_lut_bytes)
         call("mmdx_image_preprocess", ptr(px), ptr(d_desc), len(arrays), ptr(d_coef), max_trows,
              CROP, CROP, ptr(temp), ptr(out), stream())
         # the pinned staging buffer must outlive the asynchronous copy

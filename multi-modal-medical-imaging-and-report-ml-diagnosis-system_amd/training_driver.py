@@ -153,7 +153,8 @@ def save_model_to_hopsworks_model_registry(fusion_model, model_name="fusion_tran
 def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="resnet50",
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
-                   augment=None, criterion=None, uncertain=None, calibrate=None, bootstrap=0):
+                   augment=None, criterion=None, uncertain=None, calibrate=None, bootstrap=0,
+                   clahe=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -187,7 +188,19 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     bootstrap (replicates, default 0 = no intervals) is passed to evaluate(bootstrap=...): row
     bootstrap intervals of the held-out metrics (mmdx.bootstrap), so it needs val_rows > 0 too.
     out["val"] then carries "ci" and "boot", and val_auroc_micro_ci_lo / _hi and
-    val_auroc_macro_ci_lo / _hi are registered next to the point values."""
+    val_auroc_macro_ci_lo / _hi are registered next to the point values.
+
+    clahe (an mmdx.Clahe, default None = the bundle and the batches are what they were)
+    equalises the decoded pixels on the GPU before the transform (mmdx.clahe).  It is part of
+    the model's input definition, not an augmentation: it applies to the image tower's training
+    batches (before `augment`), to the fusion phase's encode and to the validation batches
+    alike, and its config() is stored under artifacts["clahe"], where inference() finds it."""
+    if clahe is not None:
+        from .clahe import Clahe
+        if not isinstance(clahe, Clahe):
+            raise TypeError(f"training_tests: clahe must be an mmdx.Clahe or None, got "
+                            f"{type(clahe).__name__}")
+        clahe.check()
     from .bootstrap import check_args
     bootstrap = check_args(bootstrap, who="training_tests")[0]
     if bootstrap and val_rows <= 0:
@@ -222,7 +235,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
 
     log("----------IMAGE ENCODER: DATASET / BATCHES----------")
     batches = LocalCXRBatches(df, _image_root_for(df), batch_size=batch_size, shuffle=True,
-                              device=dev, augment=augment, uncertain=uncertain)
+                              device=dev, augment=augment, uncertain=uncertain, clahe=clahe)
     imgs, _, y = next(iter(batches))
     log(f"batch img input shape: {tuple(imgs.shape)}, labels {tuple(y.shape)}")
 
@@ -299,7 +312,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         val_df = val_df.reset_index(drop=True)
     rows = rows.reset_index(drop=True)
     from .preprocess import preprocess_batch
-    imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev)
+    imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev, clahe=clahe)
     y_multi = torch.tensor(apply_uncertain(
         np.stack([np.asarray(v, dtype=np.float32)
                   for v in rows["disease_classification_vector"]]), uncertain),
@@ -384,7 +397,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         val = evaluate(image_encoder, text_encoder, fusion_model,
                        LocalCXRBatches(val_df, _image_root_for(val_df), batch_size=batch_size,
                                        shuffle=False, device=dev,
-                                       uncertain=None if uncertain is None else "ignore"),
+                                       uncertain=None if uncertain is None else "ignore",
+                                       clahe=clahe),
                        generate=True, gen_kwargs=gen, report_labels=val_labels,
                        criterion=None if plain_loss else criterion, calibrate=calibrate,
                        bootstrap=bootstrap)
@@ -421,6 +435,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             artifacts["loss"] = criterion.config()
         if calibration is not None:
             artifacts["calibration"] = calibration
+        if clahe is not None:
+            artifacts["clahe"] = clahe.config()
         rm = save_model_to_hopsworks_model_registry(
             fusion_model=fusion_model, text_encoder=text_encoder, image_encoder=image_encoder,
             model_name=model_name, description="CXR fusion: CNN+Text -> MLP; multi-label "
