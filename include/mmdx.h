@@ -918,6 +918,31 @@ int mmdx_cam_fwd(int dtype, const void* fmap, const float* alpha, int B, int HW,
 int mmdx_cam_resize(const float* raw, int BC, int H, int W, int Ho, int Wo, int normalize,
                     float* out, void* stream);
 
+/* ---------------------------------------------------------------- ViT explanations
+ * The transformer tower has no conv stage for Grad-CAM; its explanations are built on the
+ * attention probabilities, which the flash-style attention core never stores.  These two
+ * kernels recompute them per layer and walk the class-token row down the layers.  Both are
+ * bit-reproducible (fixed summation order, one writer per element, no atomics), independent of
+ * the launch geometry, and need no workspace.
+ *
+ * mmdx_attention_relevance: out fp32 [B][Ls][Ls] = the head-averaged attention map of one
+ * block from its qkv buffer [B*Ls][3][H][64] in `dtype`.  P_h = softmax_j(scale Q_h K_h^T)
+ * (no key mask; MFMA products with fp32 accumulation, fp32 softmax with the row maximum
+ * subtracted).  dout == NULL: out = (1/H) sum_h P_h (rows sum to 1).  dout [B*Ls][H][64] in
+ * `dtype` (the gradient of a scalar with respect to the attention core's output):
+ * out = (1/H) sum_h relu(P_h o dP_h), dP_h = dO_h V_h^T.  The head sum runs h = 0 .. H-1 in
+ * fp32.  1 <= Ls <= 256, 1 <= H <= 16, head dim 64; qkv and dout 16-byte aligned.
+ *
+ * mmdx_rollout_step: r_out[b][j] = alpha r_in[b][j] + beta sum_i r_in[b][i] abar[b][i][j], all
+ * fp32, r [B][Ls], abar [B][Ls][Ls]; i is summed in ascending order by the thread that owns
+ * column j.  (alpha, beta) = (a, 1 - a) is one layer of attention rollout with residual a,
+ * (1, 1) one layer of the relevance recursion R <- R + abar R, both for the class-token row
+ * taken from the last layer down.  Ls <= 4096; r_out must not overlap r_in. */
+int mmdx_attention_relevance(int dtype, const void* qkv, const void* dout, int B, int Ls, int H,
+                             float scale, float* out, void* stream);
+int mmdx_rollout_step(const float* r_in, const float* abar, int B, int Ls, float alpha,
+                      float beta, float* r_out, void* stream);
+
 /* ---------------------------------------------------------------- training augmentation
  * Per-image affine warp + contrast / brightness of normalised images, one launch, no workspace,
  * no atomics, bit-reproducible.  x, out fp32 [B][C][H][W] (NCHW, contiguous, out must not

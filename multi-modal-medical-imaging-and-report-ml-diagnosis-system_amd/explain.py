@@ -15,12 +15,32 @@ the same for every pixel: no trunk backward is needed.  With eval mode everywher
 
 `g` runs through the heads' own autograd Functions (Linear, fusion_linear, LayerNorm): one
 pass over B * Cs rows and one torch.autograd.grad with one-hot grad_outputs.  Only ResNet
-trunks have such a conv stage; a vit_b_16 encoder raises NotImplementedError.
+trunks have such a conv stage; on a vit_b_16 encoder grad_cam raises NotImplementedError.
+
+The ViT tower is explained from its attention probabilities instead.  With S = 197 tokens (the
+class token, then 14 x 14 patches), P_h = softmax(Q_h K_h^T / 8) of head h in layer l and
+dP_h = dO_h V_h^T = d logit_c / d P_h (dO: the gradient at the attention core's output):
+
+    plain     abar_l = mean_h P_h                      rows sum to 1
+    weighted  abar_l = mean_h relu(P_h * dP_h)         per (sample, class)
+
+    attention_rollout        R = A_{Lyr-1} ... A_s,  A_l = a I + (1 - a) abar_l   (Abnar & Zuidema)
+    transformer_attribution  R = (I + abar_{Lyr-1}) ... (I + abar_s)           (Chefer, Gur & Wolf)
+
+Only the class-token row of R is wanted: r = e_0, then r <- alpha r + beta (r abar_l) from the
+last layer down to s (functional.rollout_step), with (alpha, beta) = (a, 1 - a) or (1, 1).  The
+attention core stores no P; functional.attention_relevance recomputes abar_l from the block's
+qkv buffer.  The weighted form meets each layer's (qkv, dO) pair where the block backward
+(xlayers.vit_bwd) hands it to the attention backward.  r[1:] as [14, 14] is the map.
+`rollout_reference` / `attribution_reference` restate all of it in float64 torch on the CPU with
+explicit attention matrices: the tests' yardstick.
 
 `cam_to_image` and `overlay` are the host half (numpy / PIL): put a 224 x 224 map back on the
 original radiograph and blend it in.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -28,18 +48,35 @@ import torch
 from . import functional as F
 from .training_pipeline import IMG_SIZE
 
-__all__ = ["grad_cam", "select_classes", "cam_to_image", "overlay"]
+__all__ = ["grad_cam", "attention_rollout", "transformer_attribution", "rollout_reference",
+           "attribution_reference", "select_classes", "cam_to_image", "overlay"]
 
 RESIZE_SIZE = 256  # the shorter side before the centre crop (image_transfom_into_tensor)
+MAX_ATTRIBUTION_ROWS = 64  # B * Cs of one transformer_attribution call
+
+
+def _backbone_name(image_encoder):
+    trunk = getattr(image_encoder, "backbone", None)
+    return getattr(image_encoder, "backbone_name", type(trunk).__name__)
 
 
 def _trunk_of(image_encoder):
     trunk = getattr(image_encoder, "backbone", None)
     if not hasattr(trunk, "forward_features"):
         raise NotImplementedError(
-            f"Grad-CAM needs a convolutional last stage: the "
-            f"{getattr(image_encoder, 'backbone_name', type(trunk).__name__)} image encoder has "
-            f"none (ResNet backbones only; ViT attention rollout is not implemented)")
+            f"Grad-CAM needs a convolutional last stage: the {_backbone_name(image_encoder)} "
+            f"image encoder has none (ResNet backbones only; a ViT encoder is explained by "
+            f"attention_rollout / transformer_attribution)")
+    return trunk
+
+
+def _vit_trunk_of(image_encoder):
+    trunk = getattr(image_encoder, "backbone", None)
+    if not hasattr(trunk, "forward_attention"):
+        raise NotImplementedError(
+            f"attention rollout and transformer attribution need a transformer image tower: "
+            f"the {_backbone_name(image_encoder)} image encoder has none (vit_b_16 only; a "
+            f"ResNet encoder is explained by grad_cam)")
     return trunk
 
 
@@ -90,6 +127,249 @@ def grad_cam(image_encoder, text_encoder, fusion_model, images, input_ids, atten
     finally:
         for m, flag in was:
             m.training = flag
+
+
+# ----------------------------------------------------------------------------- ViT explanations
+def _check_vit_call(trunk, images, start_layer, rows):
+    layers = len(trunk.encoder.layers)
+    if not torch.is_tensor(images) or images.dim() != 4 or \
+            tuple(images.shape[1:]) != (3, IMG_SIZE, IMG_SIZE) or images.shape[0] < 1:
+        raise ValueError(f"the ViT tower takes images [B, 3, {IMG_SIZE}, {IMG_SIZE}], got "
+                         f"{tuple(images.shape) if torch.is_tensor(images) else type(images)}")
+    if isinstance(start_layer, bool) or not isinstance(start_layer, int) or \
+            not 0 <= start_layer < layers:
+        raise ValueError(f"start_layer must be an int in [0, {layers}), got {start_layer!r}")
+    if images.shape[0] * rows > MAX_ATTRIBUTION_ROWS:
+        raise ValueError(f"B * Cs = {images.shape[0]} * {rows} > {MAX_ATTRIBUTION_ROWS}: split "
+                         f"the batch or the classes")
+    return layers
+
+
+def _token_maps(r, lead, out_size, normalize, out):
+    """r [..., S] -> out["raw"] [..., g, g] (the patch tokens) and out["cam"]."""
+    g = math.isqrt(r.shape[-1] - 1)
+    out["raw"] = r[:, 1:].reshape(*lead, g, g).contiguous()
+    if out_size is not None:
+        out["cam"] = F.cam_resize(out["raw"], out_size, normalize)
+    return out
+
+
+def attention_rollout(image_encoder, images, residual=0.5, start_layer=0,
+                      out_size=(IMG_SIZE, IMG_SIZE), normalize=True, return_attention=False):
+    """Attention rollout (Abnar & Zuidema 2020) of a vit_b_16 image encoder: where the class
+    token's information came from.  Class-agnostic, forward only, no text tower, no heads.
+
+    images [B, 3, 224, 224] fp32.  residual a in [0, 1): the identity's share of every layer,
+    A_l = a I + (1 - a) mean_h P_h.  The layers start_layer .. last are multiplied up.
+    Returns {"rollout": [B, S] fp32 (the class-token row of the product; sums to 1),
+    "raw": [B, 14, 14] (its patch part), "cam": [B, Ho, Wo] (raw / max, bilinear;
+    out_size=None leaves it out)} and, return_attention=True, "attention": [layers, B, S, S],
+    the head-averaged maps.  Eval mode whatever the encoder's mode (restored on return); a
+    ResNet encoder raises NotImplementedError."""
+    trunk = _vit_trunk_of(image_encoder)
+    layers = _check_vit_call(trunk, images, start_layer, 1)
+    a = float(residual)
+    if not 0.0 <= a < 1.0:
+        raise ValueError(f"residual must be in [0, 1), got {residual!r}")
+    was = [(m, m.training) for m in image_encoder.modules()]
+    try:
+        image_encoder.eval()
+        with torch.no_grad():
+            _, abar = trunk.forward_attention(images)
+            B, S = abar.shape[1], abar.shape[2]
+            r = torch.zeros((B, S), dtype=torch.float32, device=abar.device)
+            r[:, 0] = 1.0
+            for li in range(layers - 1, start_layer - 1, -1):
+                r = F.rollout_step(r, abar[li], a, 1.0 - a)
+            out = _token_maps(r, (B,), out_size, normalize, {"rollout": r})
+            if return_attention:
+                out["attention"] = abar
+        return out
+    finally:
+        for m, flag in was:
+            m.training = flag
+
+
+def _relevance_walk(T, dev, r):
+    """The eager backend of xlayers.vit_bwd with the relevance recursion hooked in where the
+    block backward holds (qkv, dO); the parameter gradients are not formed."""
+    from . import xlayers as XL
+
+    class Walk(XL.Eager):
+        def __init__(self):
+            super().__init__(T, dev, True)
+            self.r = r
+
+        @staticmethod
+        def gemm_wgrad_bias(*args, **kwargs):
+            return None
+
+        def attn_bwd(self, qkv, saved, att, datt, mask, B, Ls, H, scale, p_drop, dqkv):
+            abar = F.attention_relevance(qkv, B, Ls, H, scale, dout=datt)
+            self.r = F.rollout_step(self.r, abar, 1.0, 1.0)
+            F.attention_bwd(qkv, saved, att, datt, mask, B, Ls, H, scale, p_drop, dqkv)
+
+    return Walk()
+
+
+def transformer_attribution(image_encoder, text_encoder, fusion_model, images, input_ids,
+                            attention_mask, token_type_ids=None, classes=None, start_layer=0,
+                            out_size=(IMG_SIZE, IMG_SIZE), normalize=True):
+    """Gradient-weighted attention relevance (Chefer, Gur & Wolf 2021, the self-attention rule)
+    of the disease logits for a vit_b_16 image encoder: one map per sample and class.
+
+    Arguments as grad_cam; images [B, 3, 224, 224], B * len(classes) <= 64; the layers
+    start_layer .. last take part.  Returns grad_cam's keys, {"logits": [B, n_disease] fp32,
+    "classes", "raw": [B, Cs, 14, 14] fp32, "cam": [B, Cs, Ho, Wo] (out_size=None leaves it
+    out)}, and "relevance": [B, Cs, S], the class-token row of (I + abar_last) ... (I + abar_s).
+
+    The trunk runs eagerly, outside autograd, on B * Cs replicated rows (row b * Cs + j: sample
+    b, classes[j]); only the class-token LayerNorm, `proj` and the fusion head are differentiated
+    (one torch.autograd.grad with one-hot grad_outputs), then xlayers.vit_bwd carries the
+    gradient down the blocks.  Eval mode whatever the modules' mode (restored on return), works
+    under torch.no_grad(), leaves every parameter's .grad untouched."""
+    from . import xlayers as XL
+    from .vit import _ClassTokenLNFn
+    trunk = _vit_trunk_of(image_encoder)
+    n_cls = fusion_model.disease_head.out_features
+    classes = list(range(n_cls)) if classes is None else [int(c) for c in classes]
+    if not classes or any(c < 0 or c >= n_cls for c in classes):
+        raise ValueError(f"classes must be indices in [0, {n_cls}), got {classes}")
+    Cs = len(classes)
+    layers = _check_vit_call(trunk, images, start_layer, Cs)
+    B = images.shape[0]
+    mods = (image_encoder, text_encoder, fusion_model)
+    was = [(m, m.training) for top in mods for m in top.modules()]
+    try:
+        for top in mods:
+            top.eval()
+        with torch.no_grad():
+            # row b * Cs + j carries sample b and is differentiated for classes[j]
+            h, c, kept = trunk.forward_blocks(images.repeat_interleave(Cs, dim=0), True)
+            z_txt = text_encoder(input_ids=input_ids, attention_mask=attention_mask,
+                                 token_type_ids=token_type_ids)["embeddings"]
+        with torch.enable_grad():
+            h = h.requires_grad_(True)
+            feats = _ClassTokenLNFn.apply(h, trunk.encoder.ln.weight, trunk.encoder.ln.bias)
+            t_rep = z_txt.detach().repeat_interleave(Cs, dim=0)
+            logits = fusion_model(image_encoder.proj(feats), t_rep)["disease_logits"]
+            pick = torch.zeros_like(logits)
+            pick[torch.arange(B * Cs, device=logits.device),
+                 torch.tensor(classes, device=logits.device).repeat(B)] = 1.0
+            (dh,) = torch.autograd.grad(logits, h, grad_outputs=pick)
+        with torch.no_grad():
+            S, M = c.Ls, B * Cs * c.Ls
+            r = torch.zeros((B * Cs, S), dtype=torch.float32, device=h.device)
+            r[:, 0] = 1.0
+            be = _relevance_walk(h.dtype, h.device, r)
+            gd = be.grad_bufs(XL.vit_grads(c.D, c.I))   # only the LayerNorm entries are written
+            dO = F.cast(dh.contiguous().reshape(M, c.D), h.dtype)
+            for li in range(layers - 1, start_layer - 1, -1):
+                dO = XL.vit_bwd(be, kept[li], dO, None, gd, c)
+                kept[li] = None
+            out = {"logits": logits.detach().view(B, Cs, n_cls)[:, 0].float().contiguous(),
+                   "classes": classes, "relevance": be.r.view(B, Cs, S)}
+            _token_maps(be.r, (B, Cs), out_size, normalize, out)
+        return out
+    finally:
+        for m, flag in was:
+            m.training = flag
+
+
+# ----------------------------------------------------------------------------- fp64 references
+def _ref_ln(x, w, b, eps=1e-6):
+    mu = x.mean(-1, keepdim=True)
+    var = ((x - mu) ** 2).mean(-1, keepdim=True)
+    return (x - mu) / torch.sqrt(var + eps) * w + b
+
+
+def reference_vit(state_dict, images, heads=12, track=False):
+    """A VitTrunk / RefVitTrunk state dict restated in float64 on the CPU with the attention
+    probabilities as explicit tensors of the graph: -> (feats [B, 768], [P_l [B, H, S, S]]).
+    track=True makes the token embeddings a leaf that requires grad, so that autograd can
+    differentiate a function of feats with respect to every P_l.
+    (nn.MultiheadAttention cannot serve: the weights it returns are not the tensor its output
+    was computed from, so they carry no gradient of the output.)"""
+    sd = {k: v.detach().double().cpu() for k, v in state_dict.items()}
+    x = images.detach().double().cpu()
+    B = x.shape[0]
+    w = sd["conv_proj.weight"]
+    D, _, p, _ = w.shape
+    tok = torch.nn.functional.conv2d(x, w, sd["conv_proj.bias"], stride=p)
+    tok = tok.reshape(B, D, -1).permute(0, 2, 1)
+    h = torch.cat([sd["class_token"].expand(B, -1, -1), tok], dim=1) + sd["encoder.pos_embedding"]
+    if track:
+        h.requires_grad_(True)
+    S, hd = h.shape[1], D // heads
+    probs = []
+    li = 0
+    while f"encoder.layers.encoder_layer_{li}.ln_1.weight" in sd:
+        k = f"encoder.layers.encoder_layer_{li}."
+        u = _ref_ln(h, sd[k + "ln_1.weight"], sd[k + "ln_1.bias"])
+        qkv = u @ sd[k + "self_attention.in_proj_weight"].T + sd[k + "self_attention.in_proj_bias"]
+        q, kk, v = (t.reshape(B, S, heads, hd).transpose(1, 2) for t in qkv.chunk(3, dim=-1))
+        P = torch.softmax(q @ kk.transpose(-1, -2) / math.sqrt(hd), dim=-1)
+        probs.append(P)
+        att = (P @ v).transpose(1, 2).reshape(B, S, D)
+        h = h + att @ sd[k + "self_attention.out_proj.weight"].T + \
+            sd[k + "self_attention.out_proj.bias"]
+        u = _ref_ln(h, sd[k + "ln_2.weight"], sd[k + "ln_2.bias"])
+        f = torch.nn.functional.gelu(u @ sd[k + "mlp.0.weight"].T + sd[k + "mlp.0.bias"])
+        h = h + f @ sd[k + "mlp.3.weight"].T + sd[k + "mlp.3.bias"]
+        li += 1
+    feats = _ref_ln(h[:, 0], sd["encoder.ln.weight"], sd["encoder.ln.bias"])
+    return feats, probs
+
+
+def _class_token_row(abars, alpha, beta, start_layer):
+    """e_0^T (alpha I + beta abar_last) ... (alpha I + beta abar_s) by vector steps."""
+    B, S = abars[0].shape[0], abars[0].shape[1]
+    r = torch.zeros(B, S, dtype=torch.float64)
+    r[:, 0] = 1.0
+    for A in reversed(abars[start_layer:]):
+        r = alpha * r + beta * torch.einsum("bi,bij->bj", r, A)
+    return r
+
+
+def rollout_reference(state_dict, images, residual=0.5, start_layer=0):
+    """attention_rollout in float64 torch on the CPU from a trunk's state dict:
+    {"feats": [B, 768], "attention": [layers, B, S, S], "rollout": [B, S], "raw": [B, 14, 14]}."""
+    with torch.no_grad():
+        feats, probs = reference_vit(state_dict, images)
+        abars = [P.mean(1) for P in probs]
+        r = _class_token_row(abars, float(residual), 1.0 - float(residual), start_layer)
+    g = math.isqrt(r.shape[1] - 1)
+    return {"feats": feats, "attention": torch.stack(abars), "rollout": r,
+            "raw": r[:, 1:].reshape(-1, g, g)}
+
+
+def attribution_reference(state_dict, images, head, classes=None, start_layer=0):
+    """transformer_attribution in float64 torch on the CPU.  head: feats [B, 768] float64 ->
+    logits [B, C], differentiable (proj, the fusion head with the text embeddings closed over).
+    d logit_c / d P comes from autograd through the explicit attention; the relevance is the
+    matrix recursion R <- R + abar R from the identity, of which row 0 is returned:
+    {"logits": [B, C], "classes", "relevance": [B, Cs, S], "raw": [B, Cs, 14, 14]}."""
+    with torch.enable_grad():
+        feats, probs = reference_vit(state_dict, images, track=True)
+        logits = head(feats)
+        classes = list(range(logits.shape[1])) if classes is None else [int(c) for c in classes]
+        rows = []
+        for cls in classes:
+            # (a head that does not depend on feats has a zero gradient everywhere)
+            grads = torch.autograd.grad(logits[:, cls].sum(), probs, retain_graph=True,
+                                        allow_unused=True) if logits.requires_grad \
+                else [None] * len(probs)
+            B, _, S, _ = probs[0].shape
+            R = torch.eye(S, dtype=torch.float64).expand(B, S, S).clone()
+            for P, dP in list(zip(probs, grads))[start_layer:]:
+                dP = torch.zeros_like(P) if dP is None else dP
+                abar = (P.detach() * dP).clamp(min=0).mean(1)
+                R = R + abar @ R
+            rows.append(R[:, 0])
+    rel = torch.stack(rows, 1)
+    g = math.isqrt(rel.shape[2] - 1)
+    return {"logits": logits.detach(), "classes": classes, "relevance": rel,
+            "raw": rel[:, :, 1:].reshape(rel.shape[0], len(classes), g, g)}
 
 
 def select_classes(probs, thresholds, class_names, explain):

@@ -19,6 +19,7 @@ __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
     "augment_affine", "disease_loss", "calib_fit", "reliability_bins", "clahe",
+    "attention_relevance", "rollout_step",
 ]
 
 
@@ -833,6 +834,98 @@ def cam_resize(raw, out_size, normalize=True):
     out = torch.empty((*raw.shape[:-2], Ho, Wo), dtype=torch.float32, device=raw.device)
     call("mmdx_cam_resize", ptr(raw), raw.numel() // (H * W) if H * W else 0, H, W, Ho, Wo,
          int(bool(normalize)), ptr(out), stream())
+    return out
+
+
+# ----------------------------------------------------------------------------- ViT explanations
+ATTN_REL_MAX_L, ATTN_REL_MAX_H, ATTN_REL_HD, ROLLOUT_MAX_L = 256, 16, 64, 4096
+
+
+def _shares_memory(a, b):
+    """Whether the storage ranges of two contiguous tensors overlap (host arithmetic only)."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _f32_out(name, out, shape, *inputs):
+    """The operands of an explanation wrapper checked for layout, aliasing and device (in this
+    order, so that everything but the device can be checked on the host), then `out`: the
+    caller's, or a new fp32 tensor."""
+    for i, t in enumerate(inputs):
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: operand {i} is not contiguous (never copied here)")
+    if out is not None:
+        if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape
+                or not out.is_contiguous()):
+            raise ValueError(f"{name}: out must be contiguous fp32 {list(shape)}")
+        if any(_shares_memory(out, t) for t in inputs):
+            raise ValueError(f"{name}: out shares memory with an input")
+    for t in (*inputs, *(() if out is None else (out,))):
+        if not t.is_cuda or t.device != inputs[0].device:
+            raise ValueError(f"{name}: an operand is on {t.device}; the kernel runs on the GPU, "
+                             f"all operands on one device")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=inputs[0].device)
+    return out
+
+
+def attention_relevance(qkv, B, Ls, H, scale, dout=None, out=None):
+    """The head-averaged attention map [B, Ls, Ls] fp32 of one block, recomputed from its qkv
+    buffer [B * Ls, 3, H, 64] (fp32, bf16 or fp16; any shape of B * Ls * 3 * H * 64 elements in
+    that order, e.g. the block's [B * Ls, 3 * H * 64]) by mmdx_attention_relevance:
+    P_h = softmax(scale Q_h K_h^T), no key mask.  dout=None: mean_h P_h (rows sum to 1).
+    dout [B * Ls, H, 64] in qkv's dtype, the gradient of a scalar with respect to the attention
+    core's output: mean_h relu(P_h * dP_h) with dP_h = dO_h V_h^T.  fp32 accumulation, the heads
+    summed in order, bit-reproducible.  1 <= Ls <= 256, 1 <= H <= 16.  A wrong dtype is a
+    TypeError; a wrong shape, device or layout, a limit exceeded or an `out` that shares memory
+    with an input is a ValueError; nothing is copied or launched then."""
+    name = "attention_relevance"
+    if not torch.is_tensor(qkv) or (dout is not None and not torch.is_tensor(dout)):
+        raise TypeError(f"{name} takes tensors")
+    dt = L.dtype_code(qkv.dtype)
+    if dout is not None and dout.dtype != qkv.dtype:
+        raise TypeError(f"{name}: dout is {dout.dtype}, qkv {qkv.dtype}")
+    B, Ls, H = int(B), int(Ls), int(H)
+    if B < 1 or not 1 <= Ls <= ATTN_REL_MAX_L or not 1 <= H <= ATTN_REL_MAX_H:
+        raise ValueError(f"{name}: B = {B}, Ls = {Ls}, H = {H} outside B >= 1, 1 <= Ls <= "
+                         f"{ATTN_REL_MAX_L}, 1 <= H <= {ATTN_REL_MAX_H}")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"{name}: scale = {scale}")
+    if qkv.numel() != B * Ls * 3 * H * ATTN_REL_HD:
+        raise ValueError(f"{name}: qkv {tuple(qkv.shape)} is not [{B * Ls}, 3, {H}, "
+                         f"{ATTN_REL_HD}]")
+    if dout is not None and dout.numel() != B * Ls * H * ATTN_REL_HD:
+        raise ValueError(f"{name}: dout {tuple(dout.shape)} is not [{B * Ls}, {H}, "
+                         f"{ATTN_REL_HD}]")
+    out = _f32_out(name, out, (B, Ls, Ls), qkv, *(() if dout is None else (dout,)))
+    call("mmdx_attention_relevance", dt, ptr(qkv), ptr(dout), B, Ls, H, float(scale), ptr(out),
+         stream())
+    return out
+
+
+def rollout_step(r, abar, alpha, beta, out=None):
+    """One layer of the class-token recursion: out[b, j] = alpha r[b, j] + beta sum_i r[b, i]
+    abar[b, i, j], fp32, r [B, Ls], abar [B, Ls, Ls] (mmdx_rollout_step: i summed in ascending
+    order, bit-reproducible).  (alpha, beta) = (a, 1 - a): attention rollout with residual a;
+    (1, 1): the relevance recursion.  `out` must not share memory with r or abar.  Errors as
+    attention_relevance."""
+    name = "rollout_step"
+    if not torch.is_tensor(r) or not torch.is_tensor(abar):
+        raise TypeError(f"{name} takes tensors")
+    if r.dtype != torch.float32 or abar.dtype != torch.float32:
+        raise TypeError(f"{name} takes fp32 tensors, got {r.dtype} and {abar.dtype}")
+    if r.dim() != 2 or abar.dim() != 3 or tuple(abar.shape) != (*r.shape, r.shape[1]) or \
+            r.numel() == 0:
+        raise ValueError(f"{name} takes r [B, Ls] and abar [B, Ls, Ls], got {tuple(r.shape)} "
+                         f"and {tuple(abar.shape)}")
+    B, Ls = r.shape
+    if Ls > ROLLOUT_MAX_L:
+        raise ValueError(f"{name}: Ls = {Ls} > {ROLLOUT_MAX_L}")
+    if not (np.isfinite(float(alpha)) and np.isfinite(float(beta))):
+        raise ValueError(f"{name}: alpha = {alpha}, beta = {beta}")
+    out = _f32_out(name, out, (B, Ls), r, abar)
+    call("mmdx_rollout_step", ptr(r), ptr(abar), B, Ls, float(alpha), float(beta), ptr(out),
+         stream())
     return out
 
 

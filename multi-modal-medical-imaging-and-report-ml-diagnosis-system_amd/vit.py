@@ -203,3 +203,53 @@ class VitTrunk(nn.Module):
             for blk in self.encoder.layers:
                 h = blk(h)
         return _ClassTokenLNFn.apply(h, self.encoder.ln.weight, self.encoder.ln.bias)
+
+    def block_params(self):
+        """The 12 parameters of every block, in xlayers.vit_fwd's order."""
+        out = []
+        for blk in self.encoder.layers:
+            at = blk.self_attention
+            out.append((blk.ln_1.weight, blk.ln_1.bias, at.in_proj_weight, at.in_proj_bias,
+                        at.out_proj.weight, at.out_proj.bias, blk.ln_2.weight, blk.ln_2.bias,
+                        blk.mlp[0].weight, blk.mlp[0].bias, blk.mlp[3].weight,
+                        blk.mlp[3].bias))
+        return out
+
+    def forward_blocks(self, x, keep, on_block=None):
+        """The patch tokens and the eager block bodies (xlayers.vit_fwd, the launches of
+        forward() under no_grad) without autograd: -> (last block's output [B, S, 768], c, the
+        per-block `saved` dicts when keep).  on_block(li, saved) runs after each block."""
+        T = self.compute_dtype
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected images [B,3,H,W]")
+        with torch.no_grad():
+            h = _PatchTokensFn.apply(x.float(), self.conv_proj.weight, self.conv_proj.bias,
+                                     self.class_token, self.encoder.pos_embedding, T)
+            N, S, D = h.shape
+            c = SimpleNamespace(B=N, Ls=S, D=D, H=HEADS, I=MLP_DIM, eps=EPS)
+            be = XL.Eager(T, h.device, keep)
+            h = h.reshape(N * S, D)
+            kept = []
+            for li, params in enumerate(self.block_params()):
+                h, saved = XL.vit_fwd(be, 0, h, None, params, c)
+                if on_block is not None:
+                    on_block(li, saved)
+                if keep:
+                    kept.append(saved)
+        return h.reshape(N, S, D), c, kept
+
+    def forward_attention(self, x):
+        """-> (feats [B, 768], abar [layers, B, S, S] fp32): forward()'s features under no_grad,
+        bit for bit (the same launches), and every block's head-averaged attention map
+        (functional.attention_relevance on the block's qkv buffer), for attention rollout."""
+        maps = []
+        B, scale = x.shape[0], 1.0 / math.sqrt(D_MODEL // HEADS)
+
+        def grab(li, saved):
+            qkv = saved["qkv"]
+            maps.append(F.attention_relevance(qkv, B, qkv.shape[0] // B, HEADS, scale))
+
+        h, _, _ = self.forward_blocks(x, False, grab)
+        with torch.no_grad():
+            feats = _ClassTokenLNFn.apply(h, self.encoder.ln.weight, self.encoder.ln.bias)
+        return feats, torch.stack(maps)
