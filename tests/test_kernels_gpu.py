@@ -2,6 +2,11 @@
 
 Tolerances: fp32 path (exact-f32 MFMA, different summation order) rel 1e-5 of the output
 scale; bf16 path rel 2e-2 (bf16 inputs, fp32 accumulation).
+
+The conv tests here compare the largest error of a whole tensor with that bar (one missing term
+or border tap stays under it) and skip the dgrad of channel-padded inputs;
+tests/test_conv_reference_gpu.py checks the conv kernels element by element against fp64 at
+ragged tiles, K tails, odd phases and the fp32 paths.
 """
 import math
 import pytest
