@@ -7,6 +7,12 @@ The conv tests here compare the largest error of a whole tensor with that bar (o
 or border tap stays under it) and skip the dgrad of channel-padded inputs;
 tests/test_conv_reference_gpu.py checks the conv kernels element by element against fp64 at
 ragged tiles, K tails, odd phases and the fp32 paths.
+
+test_layernorm_bce_gelu checks LayerNorm's y and dx at one shape with the same whole-tensor
+bar; tests/test_rowwise_reference_gpu.py checks the LayerNorm entry points (dgamma and dbeta,
+beta_acc, both MMDX_LN_BWD_RPW values, every vector-slot edge up to D = 2048, the finalize over
+hundreds of partial blocks) and the token kernels of text.hip and vit.hip element by element
+against the fp64 reference of tests/rowwise_ref.py.
 """
 import math
 import pytest

@@ -33,6 +33,10 @@ def _t5(layers=2, seed=0, dropout=0.0):
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_rmsnorm(dev, dt):
+    """The T5 wrappers _rms / _rms_bwd at one shape against a whole-tensor bar (dx through
+    acc - 0.5).  tests/test_rowwise_reference_gpu.py::test_rmsnorm checks mmdx_rmsnorm_fwd / _bwd
+    element by element against fp64: fp16, beta and beta_acc onto preloaded buffers, rows around
+    the 8-row wave and 32-row block splits, D up to the register limit."""
     g = torch.Generator().manual_seed(3)
     x = torch.randn(37, 512, generator=g)
     w = torch.rand(512, generator=g) + 0.5
