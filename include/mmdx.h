@@ -63,6 +63,16 @@ int mmdx_stream_destroy(void* stream);
  * TextEncoderTransformer.proj/classifier (TP:365,367), BERT dense layers (TP:360 ->
  * transformers BertModel), fusion_mlp[0] + GELU (TP:534-536), disease_head (TP:542). */
 size_t mmdx_gemm_workspace_size(int dtype, int M, int N, int K);
+/* Host only (no GPU needed): the kernel mmdx_gemm / mmdx_gemm_res launch for this problem, from
+ * the functions the launch itself calls, as "<family>/<bm>x<bn>/ns<stages>/s<splits>/k<kper>":
+ * family kload (register-staged loaders) | dma4 | dma8 (LDS-DMA kernels of 4 / 8 waves), kper
+ * the K extent of one split.  *_addr_low4: the low four bits of the operand's address.
+ * bias_sum != 0 describes mmdx_gemm_bias_grad instead (both operands R-major): the string gains
+ * the prefix "wb-fused/" (bias sums inside the split-K GEMM) or "wb-unfused/" (mmdx_gemm, then
+ * mmdx_bias_grad).  Writes a NUL-terminated string of fewer than n bytes to out. */
+int mmdx_gemm_describe(int dtype, int M, int N, int K, long lda, int a_kmajor, int a_addr_low4,
+                       long ldb, int b_kmajor, int b_addr_low4, int bias_sum, char* out,
+                       size_t n);
 /* mmdx_gemm plus a residual [M][ldc] of C's dtype added last (after the activation and
  * beta*C): C = act(alpha*A B^T + bias) + beta*C + residual; residual must not alias C.
  * Replaces: the residual adds of torchvision's EncoderBlock (x + mlp(ln_2(x)), vit_b_16). */

@@ -76,6 +76,8 @@ SIGNATURES = {
     "mmdx_stream_create": (i32, [i32, i32, C.POINTER(vp)]),
     "mmdx_stream_destroy": (i32, [vp]),
     "mmdx_gemm_workspace_size": (sz, [i32, i32, i32, i32]),
+    "mmdx_gemm_describe": (i32, [i32, i32, i32, i32, i64, i32, i32, i64, i32, i32, i32, C.c_char_p,
+                                 sz]),
     "mmdx_gemm": (i32, [i32, i32, i32, i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, vp, vp,
                         i32, f32, f32, vp, vp, sz, vp]),
     "mmdx_conv_pack_weight": (i32, [i32, CD, i32, vp, vp, vp, vp]),

@@ -115,6 +115,55 @@ static long gemm256_fwd_min_tiles() { return knobs().gemm256_fwd_min; }
 // tiles.
 static bool gemm_8w128_on() { return knobs().gemm_8w128; }
 
+// The kernel a dense GEMM launches, decided on the host from the shapes, the leading dimensions
+// and the low four address bits of the operands alone: launch_dense() instantiates what this
+// names, and mmdx_gemm_describe() prints it, so the two cannot drift.
+enum DenseFamily {
+  DENSE_KLOAD = 0,  // igemm_kernel: register-staged loaders (any alignment, any K)
+  DENSE_DMA4,       // igemm_dma_kernel, 4 waves of 64 x 64 (or the 64-wide tiles' shares)
+  DENSE_DMA8,       // igemm_dma_kernel, 8 waves: 128 x 128 as 64 x 32, 256 x 256 as 128 x 64
+};
+struct DensePath {
+  int family, bm, bn, ns;  // DenseFamily, the block tile, operand stages
+  bool va, vb;             // the operands allow 16-B vector loads (DenseK / DenseR ::vec)
+};
+
+// esize: bytes per operand element; (bm, bn, splits, kper): plan_dense's; bias_sum: the fused
+// weight + bias gradient's epilogue (EpiPartialBias), which has no 256 x 256 instantiation.
+static DensePath dense_path(int esize, int bm, int bn, int M, int N, int K, long lda, bool ak,
+                            unsigned a_low4, long ldb, bool bk, unsigned b_low4, bool bias_sum,
+                            int splits, int kper) {
+  DensePath d;
+  const int VEC = 16 / esize;
+  d.va = lda % VEC == 0 && (a_low4 & 15) == 0;
+  d.vb = ldb % VEC == 0 && (b_low4 & 15) == 0;
+  d.family = DENSE_KLOAD;
+  d.bm = bm;
+  d.bn = bn;
+  d.ns = 2;
+  if (esize != 2) return d;
+  // LDS-DMA kernel when every 16-B chunk is either wholly inside or wholly outside the
+  // operand: k-major needs K % 8 == 0, row-major needs its row count % 8 == 0
+  const long abytes = (long)(ak ? M : K) * lda * 2, bbytes = (long)(bk ? N : K) * ldb * 2;
+  const bool oka = d.va && (ak ? K % 8 == 0 : M % 8 == 0) && abytes < (1L << 31);
+  const bool okb = d.vb && (bk ? K % 8 == 0 : N % 8 == 0) && bbytes < (1L << 31);
+  if (!(oka && okb)) return d;
+  const long nwg = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+  if (bm == 128 && bn == 128 && ak && bk && !bias_sum) {
+    const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+    const long lim256 = gemm256_fwd_min_tiles();
+    if (splits == 1 && lim256 > 0 && t256 >= lim256 && K >= 128) {
+      d.family = DENSE_DMA8;
+      d.bm = d.bn = 256;
+      return d;
+    }
+  }
+  d.family = bm == 128 && bn == 128 && gemm_8w128_on() ? DENSE_DMA8 : DENSE_DMA4;
+  // three operand stages where the grid leaves one block per CU and K is long
+  if (nwg * splits <= 256 && kper >= 256) d.ns = 3;
+  return d;
+}
+
 template <typename T, int BM, int BN, bool AK, bool BKm, class Epi>
 static int launch_dense(const void* A, long lda, const void* B, long ldb, const Epi& epi,
                         int M, int N, int K, int splits, int kper, hipStream_t st) {
@@ -122,54 +171,48 @@ static int launch_dense(const void* A, long lda, const void* B, long ldb, const 
   typedef typename std::conditional<BKm, DenseK<T>, DenseR<T>>::type SB;
   typedef typename std::conditional<AK, KLoad<T, BM, SA>, RLoad<T, BM, SA>>::type LA;
   typedef typename std::conditional<BKm, KLoad<T, BN, SB>, RLoad<T, BN, SB>>::type LB;
-  constexpr int VEC = Vec16<T>::N;
-  const bool va = lda % VEC == 0 && ((uintptr_t)A & 15) == 0;
-  const bool vb = ldb % VEC == 0 && ((uintptr_t)B & 15) == 0;
-  SA sa{(const T*)A, lda, M, va};
-  SB sb{(const T*)B, ldb, N, vb};
+  const DensePath dp = dense_path((int)sizeof(T), BM, BN, M, N, K, lda, AK,
+                                  (unsigned)((uintptr_t)A & 15), ldb, BKm,
+                                  (unsigned)((uintptr_t)B & 15), HasBiasSum<Epi>::value, splits,
+                                  kper);
+  SA sa{(const T*)A, lda, M, dp.va};
+  SB sb{(const T*)B, ldb, N, dp.vb};
   if constexpr (!AK) sa.vrows = K;  // R-major: k runs over the leading-dimension rows
   if constexpr (!BKm) sb.vrows = K;
   const int nwg = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   if constexpr (sizeof(T) == 2) {
-    // LDS-DMA kernel when every 16-B chunk is either wholly inside or wholly outside the
-    // operand: k-major needs K % 8 == 0, row-major needs its row count % 8 == 0
-    const long abytes = (long)(AK ? M : K) * lda * 2, bbytes = (long)(BKm ? N : K) * ldb * 2;
-    const bool oka = va && (AK ? K % 8 == 0 : M % 8 == 0) && abytes < (1L << 31);
-    const bool okb = vb && (BKm ? K % 8 == 0 : N % 8 == 0) && bbytes < (1L << 31);
-    if (oka && okb) {
-      if constexpr (BM == 128 && BN == 128 && AK && BKm && !HasBiasSum<Epi>::value) {
+    if constexpr (BM == 128 && BN == 128 && AK && BKm && !HasBiasSum<Epi>::value) {
+      if (dp.family == DENSE_DMA8 && dp.bm == 256) {
         const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-        const long lim256 = gemm256_fwd_min_tiles();
-        if (splits == 1 && lim256 > 0 && t256 >= lim256 && K >= 128) {
-          typedef DmaK<256, SA, 64, 8> OA8;
-          typedef DmaK<256, SB, 64, 8> OB8;
-          hipLaunchKernelGGL((igemm_dma_kernel<256, 256, OA8, OB8, Epi, 2, T, 512, 2, 4>),
-                             dim3((unsigned)t256, 1, 1), dim3(512), 0, st, sa, sb, epi, M, N, K,
-                             kper);
-          MMDX_LAUNCH_CHECK();
-          return 0;
-        }
+        typedef DmaK<256, SA, 64, 8> OA8;
+        typedef DmaK<256, SB, 64, 8> OB8;
+        hipLaunchKernelGGL((igemm_dma_kernel<256, 256, OA8, OB8, Epi, 2, T, 512, 2, 4>),
+                           dim3((unsigned)t256, 1, 1), dim3(512), 0, st, sa, sb, epi, M, N, K,
+                           kper);
+        MMDX_LAUNCH_CHECK();
+        return 0;
       }
-      if constexpr (BM == 128 && BN == 128) {
-        if (gemm_8w128_on()) {  // 8 waves of 64 x 32
-          typedef typename std::conditional<AK, DmaK<128, SA, 64, 8>,
-                                            DmaR<128, SA, 64, 8>>::type OA8;
-          typedef typename std::conditional<BKm, DmaK<128, SB, 64, 8>,
-                                            DmaR<128, SB, 64, 8>>::type OB8;
-          if ((long)nwg * splits <= 256 && kper >= 256)
-            hipLaunchKernelGGL((igemm_dma_kernel<128, 128, OA8, OB8, Epi, 3, T, 512, 2, 4>),
-                               dim3(nwg, 1, splits), dim3(512), 0, st, sa, sb, epi, M, N, K, kper);
-          else
-            hipLaunchKernelGGL((igemm_dma_kernel<128, 128, OA8, OB8, Epi, 2, T, 512, 2, 4>),
-                               dim3(nwg, 1, splits), dim3(512), 0, st, sa, sb, epi, M, N, K, kper);
-          MMDX_LAUNCH_CHECK();
-          return 0;
-        }
+    }
+    if constexpr (BM == 128 && BN == 128) {
+      if (dp.family == DENSE_DMA8) {  // 8 waves of 64 x 32
+        typedef typename std::conditional<AK, DmaK<128, SA, 64, 8>,
+                                          DmaR<128, SA, 64, 8>>::type OA8;
+        typedef typename std::conditional<BKm, DmaK<128, SB, 64, 8>,
+                                          DmaR<128, SB, 64, 8>>::type OB8;
+        if (dp.ns == 3)
+          hipLaunchKernelGGL((igemm_dma_kernel<128, 128, OA8, OB8, Epi, 3, T, 512, 2, 4>),
+                             dim3(nwg, 1, splits), dim3(512), 0, st, sa, sb, epi, M, N, K, kper);
+        else
+          hipLaunchKernelGGL((igemm_dma_kernel<128, 128, OA8, OB8, Epi, 2, T, 512, 2, 4>),
+                             dim3(nwg, 1, splits), dim3(512), 0, st, sa, sb, epi, M, N, K, kper);
+        MMDX_LAUNCH_CHECK();
+        return 0;
       }
+    }
+    if (dp.family == DENSE_DMA4) {
       typedef typename std::conditional<AK, DmaK<BM, SA>, DmaR<BM, SA>>::type OA;
       typedef typename std::conditional<BKm, DmaK<BN, SB>, DmaR<BN, SB>>::type OB;
-      // three operand stages where the grid leaves one block per CU and K is long
-      if ((long)nwg * splits <= 256 && kper >= 256)
+      if (dp.ns == 3)
         hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, OA, OB, Epi, 3, T>),
                            dim3(nwg, 1, splits), dim3(NT), 0, st, sa, sb, epi, M, N, K, kper);
       else

@@ -14,10 +14,11 @@ import torch.nn.functional as tF
 
 import bn_ref
 
-BF16, F32 = torch.bfloat16, torch.float32
-H_T = {BF16: 2.0 ** -8, F32: 2.0 ** -24}   # one round to nearest on store
+BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
+H_T = {BF16: 2.0 ** -8, F16: 2.0 ** -11, F32: 2.0 ** -24}   # one round to nearest on store
 ACC = 2e-5                                  # fp32 accumulation in any order, times sum |terms|
 EXACT_BF16 = 256.0                          # integers up to here are bf16 values
+EXACT_F16 = 2048.0                          # ... and fp16 values
 EXACT_F32 = 2.0 ** 24                       # integers below here are fp32 values
 
 
@@ -235,13 +236,16 @@ def operands(cid, family):
 
 
 # ------------------------------------------------------------------------------ comparisons
-def check_exact_preconditions(ref, n_terms, dt_stored, what):
+def check_exact_preconditions(ref, n_terms, dt_stored, what, step=1.0):
     """What makes an exact comparison legitimate, from the reference alone: every value an
-    integer; storable in the output dtype (|v| <= 256 in bf16, < 2^24 in fp32); and the sum of
-    |terms| (at most n_terms: every |term| is 0 or 1) below 2^24, so that an fp32 accumulator
-    holds every partial sum in any order."""
-    assert torch.equal(ref, ref.round()), f"{what}: the reference is not integer-valued"
-    top = EXACT_BF16 if dt_stored == BF16 else EXACT_F32 - 1
+    integer; storable in the output dtype (|v| <= 256 in bf16, <= 2048 in fp16, < 2^24 in fp32);
+    and the sum of |terms| (at most n_terms: every |term| is 0 or 1) below 2^24, so that an fp32
+    accumulator holds every partial sum in any order.  step (a power of two, 1 by default): the
+    values are multiples of step instead, storable up to step times those limits (half-integers
+    within 128 in bf16)."""
+    assert torch.equal(ref, (ref / step).round() * step), \
+        f"{what}: the reference is not integer-valued" + ("" if step == 1.0 else f" / {step}")
+    top = {BF16: EXACT_BF16, F16: EXACT_F16}.get(dt_stored, EXACT_F32 - 1) * step
     assert ref.abs().max().item() <= top, f"{what}: max |ref| {ref.abs().max().item()} > {top}"
     assert n_terms < EXACT_F32, f"{what}: {n_terms} terms can exceed 2^24"
 

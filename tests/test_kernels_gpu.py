@@ -13,6 +13,14 @@ bar; tests/test_rowwise_reference_gpu.py checks the LayerNorm entry points (dgam
 beta_acc, both MMDX_LN_BWD_RPW values, every vector-slot edge up to D = 2048, the finalize over
 hundreds of partial blocks) and the token kernels of text.hip and vit.hip element by element
 against the fp64 reference of tests/rowwise_ref.py.
+
+The GEMM tests here (test_gemm*, test_bias_grad, and tests/test_gemm8_gpu.py) use the same
+whole-tensor bar on randn operands at K a multiple of 8, or compare kernels that share loaders
+and epilogue bit for bit: one missing product, one dropped 8-element K tail or one skipped split
+passes.  tests/test_gemm_reference_gpu.py checks the dense GEMM entry points element by element
+against the fp64 reference of tests/gemm_ref.py: K tails, ragged tiles of every size, 2 to 7
+splits through both reduces, padded and misaligned operands, alpha != 1, every epilogue input,
+the fused weight + bias gradient and MMDX_BIAS_GRAD_GEMM=1.
 """
 import math
 import pytest
