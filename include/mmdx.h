@@ -953,6 +953,35 @@ int mmdx_attention_relevance(int dtype, const void* qkv, const void* dout, int B
 int mmdx_rollout_step(const float* r_in, const float* abar, int B, int Ls, float alpha,
                       float beta, float* r_out, void* stream);
 
+/* ---------------------------------------------------------------- text explanations
+ * mmdx_token_relevance_step: one layer of the relevance recursion for a row vector, fused with
+ * the recomputation of the attention probabilities under a key mask, in ONE launch that never
+ * writes the [Ls][Ls] map:
+ *   P_h[i][j] = softmax over the real keys j of (scale Q_h[i] . K_h[j]); exactly 0 for a masked j
+ *   abar      = (1/H) sum_h relu(P_h o dP_h), dP_h = dO_h V_h^T   (dout given)
+ *               (1/H) sum_h P_h                                   (dout == NULL)
+ *   r_out[b][j] = alpha r_in[b][j] + beta sum_i r_in[b][i] abar[b][i][j]
+ * qkv [B*Ls][3][H][64] and dout [B*Ls][H][64] in `dtype` as for mmdx_attention_relevance; mask
+ * int64 [B][Ls], 1 = a real token (NULL: all real), the tensor the attention forward takes; it
+ * applies to the keys only (every query row is computed).  A sample without a real key has
+ * abar = 0, so r_out = alpha r_in; nothing is NaN or inf.  A masked column j gets alpha r_in[j]
+ * exactly.  r_in, r_out fp32 [B][Ls], not overlapping.  1 <= Ls <= 256, 1 <= H <= 16, head dim
+ * 64; qkv and dout 16-byte aligned.
+ *
+ * No float atomics, bit-reproducible, and row b depends neither on B nor on the other samples:
+ * a workgroup adds its 32 queries in a fixed order, and the ceil(Ls / 32) workgroups of a sample
+ * meet through the workspace, where the last one to arrive adds their partial rows in tile order.
+ * The workspace (mmdx_token_relevance_workspace_size bytes, 16-byte aligned; 0 for Ls <= 32, then
+ * NULL will do) starts with one integer counter per sample, B in all, padded to 16 bytes: these
+ * must be ZERO before the first launch on a buffer; every launch leaves them zero.  The partial
+ * rows follow them, so a buffer is reused as it is only by launches of the same B (another B:
+ * zero the counters again).  Launches that share a workspace must be ordered (one stream). */
+size_t mmdx_token_relevance_workspace_size(int B, int Ls);
+int mmdx_token_relevance_step(int dtype, const void* qkv, const void* dout, const int64_t* mask,
+                              const float* r_in, int B, int Ls, int H, float scale, float alpha,
+                              float beta, float* r_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ---------------------------------------------------------------- training augmentation
  * Per-image affine warp + contrast / brightness of normalised images, one launch, no workspace,
  * no atomics, bit-reproducible.  x, out fp32 [B][C][H][W] (NCHW, contiguous, out must not

@@ -8,7 +8,7 @@ from . import _lib  # noqa: F401  (lazy: the .so loads on first kernel call)
 from .training_pipeline import (  # noqa: F401
     BCEWithLogitsLoss, DISEASES, FusionTransformerModel, IMG_SIZE, ImageEncoderCNN,
     TextEncoderTransformer, get_compute_dtype, image_transfom_into_tensor,
-    set_compute_dtype, tokenize_patient_details)
+    set_compute_dtype, token_strings, tokenize_patient_details)
 from .optim import AdamW, clip_grad_norm_  # noqa: F401
 from .amp import GradScaler  # noqa: F401
 from .preprocess import preprocess_batch  # noqa: F401

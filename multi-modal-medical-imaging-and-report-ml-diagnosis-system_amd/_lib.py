@@ -228,6 +228,9 @@ SIGNATURES = {
     "mmdx_cam_resize": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mmdx_attention_relevance": (i32, [i32, vp, vp, i32, i32, i32, f32, vp, vp]),
     "mmdx_rollout_step": (i32, [vp, vp, i32, i32, f32, f32, vp, vp]),
+    "mmdx_token_relevance_workspace_size": (sz, [i32, i32]),
+    "mmdx_token_relevance_step": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp,
+                                        vp, sz, vp]),
     "mmdx_augment_affine": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),
                                   i32, vp, vp]),
     "mmdx_clahe_desc_size": (sz, []),

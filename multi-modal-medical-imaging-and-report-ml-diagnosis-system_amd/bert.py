@@ -209,6 +209,39 @@ class BertModel(nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
+    def forward_layers(self, input_ids, attention_mask, token_type_ids, keep, on_layer=None):
+        """The embeddings and the eager layer bodies (xlayers.bert_fwd, the launches of forward()
+        under no_grad in eval mode: p = pa = 0) without autograd: -> (last hidden state
+        [B, Ls, D], c, the per-layer `saved` dicts when keep).  on_layer(li, saved) runs after
+        each layer.  The counterpart of VitTrunk.forward_blocks, for mmdx.explain."""
+        T = self.compute_dtype
+        L.require_device(input_ids)
+        with torch.no_grad():
+            ids = input_ids.long().contiguous()
+            B, Ls = ids.shape
+            mask = (attention_mask.long().contiguous() if attention_mask is not None
+                    else torch.ones_like(ids))
+            tt = (token_type_ids.long().contiguous() if token_type_ids is not None
+                  else torch.zeros_like(ids))
+            e = self.embeddings
+            h = _EmbedFn.apply(ids, tt, e.word_embeddings.weight, e.position_embeddings.weight,
+                               e.token_type_embeddings.weight, e.LayerNorm.weight,
+                               e.LayerNorm.bias, self.config.layer_norm_eps, T)
+            D = h.shape[-1]
+            c = SimpleNamespace(B=B, Ls=Ls, D=D, H=self.config.num_attention_heads,
+                                I=self.config.intermediate_size, eps=self.config.layer_norm_eps,
+                                p=0.0, pa=0.0)
+            be = XL.Eager(T, h.device, keep)
+            h = h.reshape(B * Ls, D)
+            kept = []
+            for li, layer in enumerate(self.encoder.layer):
+                h, saved = XL.bert_fwd(be, 0, h, mask, layer.params(), c)
+                if on_layer is not None:
+                    on_layer(li, saved)
+                if keep:
+                    kept.append(saved)
+        return h.reshape(B, Ls, D), c, kept
+
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, return_dict=True):
         T = self.compute_dtype
         L.require_device(input_ids)

@@ -95,6 +95,28 @@ __device__ __forceinline__ bool cls_last_block(unsigned* counter) {
   return ticket_s == gridDim.x - 1;
 }
 
+// The same hand-off for a grid that holds several independent groups of `nblocks` blocks, each
+// group with a counter of its own (token_relevance_step_kernel: the query tiles of one sample).
+// (A form of its own: routing the one above through it changed the instructions of its users.)
+__device__ __forceinline__ bool cls_last_of_group(unsigned* counter, unsigned nblocks) {
+  __shared__ unsigned ticket_s;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned ticket =
+        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket == nblocks - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    ticket_s = ticket;
+  }
+  __syncthreads();
+  return ticket_s == nblocks - 1;
+}
+
 // The last block's walk over the partials: thread tid takes the blocks tid / C, tid / C + R, ...
 // of class tid % C, in that order; f(blk, c) accumulates into the caller's registers.
 template <typename F>

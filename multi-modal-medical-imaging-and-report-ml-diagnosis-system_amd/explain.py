@@ -35,6 +35,15 @@ qkv buffer.  The weighted form meets each layer's (qkv, dO) pair where the block
 `rollout_reference` / `attribution_reference` restate all of it in float64 torch on the CPU with
 explicit attention matrices: the tests' yardstick.
 
+The BERT text tower gets the same two explanations per token (text_rollout, text_attribution).
+Two things differ.  Its attention has a key mask: P_h is the softmax over the REAL keys, a pad's
+probability is exactly 0.  And it pools by the mean over the real tokens, not by a class token,
+so the recursion starts at r = mask / n_real and yields (1 / n) sum_{i real} R[i, :].  One
+launch per layer (functional.token_relevance_step) recomputes P under the mask and applies
+r <- alpha r + beta (r abar_l) without ever writing abar_l.  `text_rollout_reference` /
+`text_attribution_reference` are the float64 yardsticks; `merge_wordpieces` folds "##" pieces
+back into words for display.
+
 `cam_to_image` and `overlay` are the host half (numpy / PIL): put a 224 x 224 map back on the
 original radiograph and blend it in.
 """
@@ -49,7 +58,9 @@ from . import functional as F
 from .training_pipeline import IMG_SIZE
 
 __all__ = ["grad_cam", "attention_rollout", "transformer_attribution", "rollout_reference",
-           "attribution_reference", "select_classes", "cam_to_image", "overlay"]
+           "attribution_reference", "select_classes", "cam_to_image", "overlay",
+           "text_attribution", "text_rollout", "text_attribution_reference",
+           "text_rollout_reference", "merge_wordpieces"]
 
 RESIZE_SIZE = 256  # the shorter side before the centre crop (image_transfom_into_tensor)
 MAX_ATTRIBUTION_ROWS = 64  # B * Cs of one transformer_attribution call
@@ -190,9 +201,11 @@ def attention_rollout(image_encoder, images, residual=0.5, start_layer=0,
             m.training = flag
 
 
-def _relevance_walk(T, dev, r):
-    """The eager backend of xlayers.vit_bwd with the relevance recursion hooked in where the
-    block backward holds (qkv, dO); the parameter gradients are not formed."""
+def _relevance_walk(T, dev, r, fused=False):
+    """The eager backend of xlayers.vit_bwd / bert_bwd with the relevance recursion hooked in
+    where the layer backward holds (qkv, dO, mask); the parameter gradients are not formed.
+    fused (the text tower): one token_relevance_step launch that honours the key mask and
+    writes no map, instead of the attention_relevance + rollout_step pair."""
     from . import xlayers as XL
 
     class Walk(XL.Eager):
@@ -205,8 +218,12 @@ def _relevance_walk(T, dev, r):
             return None
 
         def attn_bwd(self, qkv, saved, att, datt, mask, B, Ls, H, scale, p_drop, dqkv):
-            abar = F.attention_relevance(qkv, B, Ls, H, scale, dout=datt)
-            self.r = F.rollout_step(self.r, abar, 1.0, 1.0)
+            if fused:
+                self.r = F.token_relevance_step(self.r, qkv, B, Ls, H, scale, 1.0, 1.0, mask,
+                                                dout=datt)
+            else:
+                abar = F.attention_relevance(qkv, B, Ls, H, scale, dout=datt)
+                self.r = F.rollout_step(self.r, abar, 1.0, 1.0)
             F.attention_bwd(qkv, saved, att, datt, mask, B, Ls, H, scale, p_drop, dqkv)
 
     return Walk()
@@ -274,6 +291,152 @@ def transformer_attribution(image_encoder, text_encoder, fusion_model, images, i
     finally:
         for m, flag in was:
             m.training = flag
+
+
+# ----------------------------------------------------------------------------- text explanations
+def _bert_of(text_encoder):
+    enc = getattr(text_encoder, "encoder", None)
+    if not hasattr(enc, "forward_layers"):
+        raise NotImplementedError(
+            f"token relevance needs a transformer text tower: the "
+            f"{getattr(text_encoder, 'model_name', type(enc).__name__)} text encoder has no "
+            f"attention (BERT towers only)")
+    return enc
+
+
+def _check_text_call(enc, input_ids, attention_mask, start_layer, rows):
+    layers = len(enc.encoder.layer)
+    if not torch.is_tensor(input_ids) or input_ids.dim() != 2 or input_ids.shape[0] < 1 or \
+            not torch.is_tensor(attention_mask) or attention_mask.shape != input_ids.shape:
+        raise ValueError("the text tower takes input_ids and attention_mask [B, Ls]")
+    if not 1 <= input_ids.shape[1] <= F.ATTN_REL_MAX_L:
+        raise ValueError(f"Ls = {input_ids.shape[1]} outside [1, {F.ATTN_REL_MAX_L}]")
+    if isinstance(start_layer, bool) or not isinstance(start_layer, int) or \
+            not 0 <= start_layer < layers:
+        raise ValueError(f"start_layer must be an int in [0, {layers}), got {start_layer!r}")
+    if input_ids.shape[0] * rows > MAX_ATTRIBUTION_ROWS:
+        raise ValueError(f"B * Cs = {input_ids.shape[0]} * {rows} > {MAX_ATTRIBUTION_ROWS}: "
+                         f"split the batch or the classes")
+    if int((attention_mask != 0).sum(1).min()) == 0:
+        raise ValueError("a row of attention_mask has no real token: its mean pool is undefined")
+    return layers
+
+
+def _mean_pool_start(mask):
+    """The recursion's start vector for a tower pooled by the mean over the real tokens:
+    mask / n_real, fp32 [B, Ls] (the class-token towers start at e_0)."""
+    m = (mask != 0).float()
+    return (m / m.sum(1, keepdim=True)).contiguous()
+
+
+def text_attribution(image_encoder, text_encoder, fusion_model, images, input_ids,
+                     attention_mask, token_type_ids=None, classes=None, start_layer=0):
+    """Gradient-weighted attention relevance (Chefer, Gur & Wolf 2021, the self-attention rule)
+    of the disease logits for the tokens of a BERT text tower: one score per sample, class and
+    token.  Arguments as grad_cam; B * len(classes) <= 64, Ls <= 256; the layers start_layer ..
+    last take part.  Returns {"logits": [B, n_disease] fp32, "classes", "relevance":
+    [B, Cs, Ls] fp32}.
+
+    The tower pools by the mean over the real tokens, so the recursion starts at r = mask /
+    n_real and "relevance" is (1 / n) sum_{i real} R[i, :] with R = (I + abar_last) ... (I +
+    abar_s); the attention probabilities are those over the real keys, and a pad's relevance is
+    exactly 0.  The layers run eagerly, outside autograd, on B * Cs replicated rows (row
+    b * Cs + j: sample b, classes[j]); only the mean pool, `proj` and the fusion head are
+    differentiated (one torch.autograd.grad with one-hot grad_outputs; the image embedding is
+    computed once), then xlayers.bert_bwd carries the gradient down the layers, with one
+    functional.token_relevance_step per layer where it holds (qkv, dO, mask).  Eval mode whatever
+    the modules' mode (restored on return), works under torch.no_grad(), leaves every parameter's
+    .grad untouched.  A row without a real token is a ValueError; an embed-mean or BiLSTM tower
+    raises NotImplementedError."""
+    from . import xlayers as XL
+    enc = _bert_of(text_encoder)
+    n_cls = fusion_model.disease_head.out_features
+    classes = list(range(n_cls)) if classes is None else [int(c) for c in classes]
+    if not classes or any(c < 0 or c >= n_cls for c in classes):
+        raise ValueError(f"classes must be indices in [0, {n_cls}), got {classes}")
+    Cs = len(classes)
+    layers = _check_text_call(enc, input_ids, attention_mask, start_layer, Cs)
+    B, Ls = input_ids.shape
+    mods = (image_encoder, text_encoder, fusion_model)
+    was = [(m, m.training) for top in mods for m in top.modules()]
+    try:
+        for top in mods:
+            top.eval()
+        with torch.no_grad():
+            z_img = image_encoder(images)["embeddings"]
+            # row b * Cs + j carries sample b and is differentiated for classes[j]
+            mask = attention_mask.long().repeat_interleave(Cs, dim=0).contiguous()
+            tt = None if token_type_ids is None else token_type_ids.repeat_interleave(Cs, dim=0)
+            h, c, kept = enc.forward_layers(input_ids.repeat_interleave(Cs, dim=0), mask, tt,
+                                            True)
+        with torch.enable_grad():
+            h = h.requires_grad_(True)
+            z_txt = text_encoder.proj(text_encoder.mean_pool(h, mask))
+            # (the image tower may compute in another dtype: a ResNet has no fp16 path)
+            z_rep = F.cast(z_img.detach().repeat_interleave(Cs, dim=0).contiguous(), z_txt.dtype)
+            logits = fusion_model(z_rep, z_txt)["disease_logits"]
+            pick = torch.zeros_like(logits)
+            pick[torch.arange(B * Cs, device=logits.device),
+                 torch.tensor(classes, device=logits.device).repeat(B)] = 1.0
+            (dh,) = torch.autograd.grad(logits, h, grad_outputs=pick)
+        with torch.no_grad():
+            be = _relevance_walk(h.dtype, h.device, _mean_pool_start(mask), fused=True)
+            gd = be.grad_bufs(XL.bert_grads(c.D, c.I))   # only the LayerNorm entries are written
+            dO = F.cast(dh.contiguous().reshape(B * Cs * Ls, c.D), h.dtype)
+            for li in range(layers - 1, start_layer - 1, -1):
+                dO = XL.bert_bwd(be, kept[li], dO, mask, gd, c)
+                kept[li] = None
+        return {"logits": logits.detach().view(B, Cs, n_cls)[:, 0].float().contiguous(),
+                "classes": classes, "relevance": be.r.view(B, Cs, Ls)}
+    finally:
+        for m, flag in was:
+            m.training = flag
+
+
+def text_rollout(text_encoder, input_ids, attention_mask, token_type_ids=None, residual=0.5,
+                 start_layer=0):
+    """Attention rollout (Abnar & Zuidema 2020) of a BERT text tower with the key mask: where
+    the mean-pooled embedding's information came from.  Class-agnostic, forward only.
+    A_l = a I + (1 - a) mean_h P_h with the residual a in [0, 1); the start vector is mask /
+    n_real as in text_attribution.  Returns {"rollout": [B, Ls] fp32}: each row sums to 1, pads
+    are exactly 0.  Eval mode whatever the encoder's mode (restored on return)."""
+    enc = _bert_of(text_encoder)
+    layers = _check_text_call(enc, input_ids, attention_mask, start_layer, 1)
+    a = float(residual)
+    if not 0.0 <= a < 1.0:
+        raise ValueError(f"residual must be in [0, 1), got {residual!r}")
+    was = [(m, m.training) for m in text_encoder.modules()]
+    try:
+        text_encoder.eval()
+        qkvs = []
+        mask = attention_mask.long().contiguous()
+        _, c, _ = enc.forward_layers(input_ids, mask, token_type_ids, False,
+                                     lambda li, saved: qkvs.append(saved["qkv"]))
+        with torch.no_grad():
+            r = _mean_pool_start(mask)
+            scale = 1.0 / math.sqrt(c.D // c.H)
+            for li in range(layers - 1, start_layer - 1, -1):
+                r = F.token_relevance_step(r, qkvs[li], c.B, c.Ls, c.H, scale, a, 1.0 - a, mask)
+        return {"rollout": r}
+    finally:
+        for m, flag in was:
+            m.training = flag
+
+
+def merge_wordpieces(tokens, scores):
+    """WordPiece tokens and their scores -> (words, scores): a "##" continuation piece is
+    appended to the word before it and its score added to that word's."""
+    if len(tokens) != len(scores):
+        raise ValueError(f"{len(tokens)} tokens, {len(scores)} scores")
+    words, sums = [], []
+    for tok, sc in zip(tokens, scores):
+        if tok.startswith("##") and len(tok) > 2 and words:
+            words[-1] += tok[2:]
+            sums[-1] += float(sc)
+        else:
+            words.append(tok)
+            sums.append(float(sc))
+    return words, sums
 
 
 # ----------------------------------------------------------------------------- fp64 references
@@ -370,6 +533,117 @@ def attribution_reference(state_dict, images, head, classes=None, start_layer=0)
     g = math.isqrt(rel.shape[2] - 1)
     return {"logits": logits.detach(), "classes": classes, "relevance": rel,
             "raw": rel[:, :, 1:].reshape(rel.shape[0], len(classes), g, g)}
+
+
+def reference_bert(state_dict, input_ids, attention_mask, token_type_ids=None, heads=12,
+                   track=False):
+    """A BertModel state dict (transformers' keys; a text tower's "encoder." prefix is accepted)
+    restated in float64 on the CPU with the attention probabilities as explicit tensors of the
+    graph: -> (last hidden state [B, Ls, D], [P_l [B, H, Ls, Ls]]).  BERT's embedding sum and
+    LayerNorm (eps 1e-12), post-LN layers, exact-erf GELU; the softmax runs over the real keys
+    (a masked key's probability is exactly 0), every query row is computed.  track=True makes
+    the embeddings a leaf that requires grad (see reference_vit)."""
+    pre = "encoder." if "encoder.embeddings.word_embeddings.weight" in state_dict else ""
+    sd = {k[len(pre):]: v.detach().double().cpu() for k, v in state_dict.items()
+          if k.startswith(pre) and v.is_floating_point()}
+    ids = input_ids.detach().long().cpu()
+    B, Ls = ids.shape
+    real = attention_mask.detach().cpu() != 0
+    if not real.any(1).all():
+        raise ValueError("a row of attention_mask has no real token")
+    tt = torch.zeros_like(ids) if token_type_ids is None else token_type_ids.detach().long().cpu()
+    eps = 1e-12
+    e = "embeddings."
+    h = sd[e + "word_embeddings.weight"][ids] + sd[e + "position_embeddings.weight"][:Ls] + \
+        sd[e + "token_type_embeddings.weight"][tt]
+    h = _ref_ln(h, sd[e + "LayerNorm.weight"], sd[e + "LayerNorm.bias"], eps)
+    if track:
+        h.requires_grad_(True)
+    D = h.shape[-1]
+    hd = D // heads
+    neg = torch.zeros(B, 1, 1, Ls, dtype=torch.float64).masked_fill(~real[:, None, None, :],
+                                                                    -math.inf)
+    probs = []
+    li = 0
+    while f"encoder.layer.{li}.attention.self.query.weight" in sd:
+        k = f"encoder.layer.{li}."
+
+        def lin(x, name):
+            return x @ sd[k + name + ".weight"].T + sd[k + name + ".bias"]
+
+        q, kk, v = (lin(h, "attention.self." + n).reshape(B, Ls, heads, hd).transpose(1, 2)
+                    for n in ("query", "key", "value"))
+        P = torch.softmax(q @ kk.transpose(-1, -2) / math.sqrt(hd) + neg, dim=-1)
+        probs.append(P)
+        att = (P @ v).transpose(1, 2).reshape(B, Ls, D)
+        h1 = _ref_ln(lin(att, "attention.output.dense") + h,
+                     sd[k + "attention.output.LayerNorm.weight"],
+                     sd[k + "attention.output.LayerNorm.bias"], eps)
+        f = torch.nn.functional.gelu(lin(h1, "intermediate.dense"))
+        h = _ref_ln(lin(f, "output.dense") + h1, sd[k + "output.LayerNorm.weight"],
+                    sd[k + "output.LayerNorm.bias"], eps)
+        li += 1
+    return h, probs
+
+
+def _masked_mean(x, real):
+    """The mean over the real positions of dim 1: x [B, Ls, ...], real [B, Ls] bool."""
+    w = real.double() / real.sum(1, keepdim=True)
+    return torch.einsum("bi,bi...->b...", w, x)
+
+
+def _mean_pool_row(abars, real, alpha, beta, start_layer):
+    """(mask / n)^T (alpha I + beta abar_last) ... (alpha I + beta abar_s) by vector steps."""
+    r = real.double() / real.sum(1, keepdim=True)
+    for A in reversed(abars[start_layer:]):
+        r = alpha * r + beta * torch.einsum("bi,bij->bj", r, A)
+    return r
+
+
+def text_rollout_reference(state_dict, input_ids, attention_mask, token_type_ids=None,
+                           residual=0.5, start_layer=0, heads=12):
+    """text_rollout in float64 torch on the CPU from a text tower's (or BertModel's) state dict:
+    {"hidden": [B, Ls, D], "attention": [layers, B, Ls, Ls], "rollout": [B, Ls]}."""
+    with torch.no_grad():
+        h, probs = reference_bert(state_dict, input_ids, attention_mask, token_type_ids, heads)
+        abars = [P.mean(1) for P in probs]
+        real = attention_mask.detach().cpu() != 0
+        r = _mean_pool_row(abars, real, float(residual), 1.0 - float(residual), start_layer)
+    return {"hidden": h, "attention": torch.stack(abars), "rollout": r}
+
+
+def text_attribution_reference(state_dict, input_ids, attention_mask, head, token_type_ids=None,
+                               classes=None, start_layer=0, heads=12):
+    """text_attribution in float64 torch on the CPU.  head: the mean-pooled hidden state
+    [B, D] float64 -> logits [B, C], differentiable (the tower's proj, the fusion head with the
+    image embeddings closed over).  d logit_c / d P comes from autograd through the explicit
+    attention; the relevance is the matrix recursion R <- R + abar R from the identity, of which
+    the mean over the real rows is returned: {"logits": [B, C], "classes", "relevance":
+    [B, Cs, Ls], "matrix": [B, Cs, Ls, Ls], "abar": per class the layers' [B, Ls, Ls]}."""
+    real = attention_mask.detach().cpu() != 0
+    with torch.enable_grad():
+        h, probs = reference_bert(state_dict, input_ids, attention_mask, token_type_ids, heads,
+                                  track=True)
+        logits = head(_masked_mean(h, real))
+        classes = list(range(logits.shape[1])) if classes is None else [int(c) for c in classes]
+        rows, mats, maps = [], [], []
+        for cls in classes:
+            grads = torch.autograd.grad(logits[:, cls].sum(), probs, retain_graph=True,
+                                        allow_unused=True) if logits.requires_grad \
+                else [None] * len(probs)
+            B, _, S, _ = probs[0].shape
+            R = torch.eye(S, dtype=torch.float64).expand(B, S, S).clone()
+            abars = []
+            for P, dP in zip(probs, grads):
+                dP = torch.zeros_like(P) if dP is None else dP
+                abars.append((P.detach() * dP).clamp(min=0).mean(1))
+            for abar in abars[start_layer:]:
+                R = R + abar @ R
+            rows.append(_masked_mean(R, real))
+            mats.append(R)
+            maps.append(abars)
+    return {"logits": logits.detach(), "classes": classes, "relevance": torch.stack(rows, 1),
+            "matrix": torch.stack(mats, 1), "abar": maps}
 
 
 def select_classes(probs, thresholds, class_names, explain):

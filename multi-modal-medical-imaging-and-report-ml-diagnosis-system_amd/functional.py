@@ -19,7 +19,7 @@ __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
     "augment_affine", "disease_loss", "calib_fit", "reliability_bins", "clahe",
-    "attention_relevance", "rollout_step",
+    "attention_relevance", "rollout_step", "token_relevance_step",
 ]
 
 
@@ -926,6 +926,75 @@ def rollout_step(r, abar, alpha, beta, out=None):
     out = _f32_out(name, out, (B, Ls), r, abar)
     call("mmdx_rollout_step", ptr(r), ptr(abar), B, Ls, float(alpha), float(beta), ptr(out),
          stream())
+    return out
+
+
+# ----------------------------------------------------------------------------- text explanations
+# token_relevance_step's workspace per (device, stream, B): the kernel needs the B counters at
+# its head zero before the first launch and leaves them zero, so one zero-filled buffer serves
+# every later call of that batch size on that stream and the call itself stays a single launch.
+# (Another B moves the boundary between the counters and the partial rows: a buffer of its own.)
+_TOKEN_WS: dict = {}
+
+
+def _token_workspace(B, Ls, dev):
+    n = L.lib().mmdx_token_relevance_workspace_size(B, Ls)
+    if n == 0:
+        return None, 0
+    key = (dev.index, stream(), B)
+    w = _TOKEN_WS.get(key)
+    if w is None or w.numel() < n:
+        w = _TOKEN_WS[key] = torch.zeros(n, dtype=torch.uint8, device=dev)
+    return w, w.numel()
+
+
+def token_relevance_step(r, qkv, B, Ls, H, scale, alpha, beta, mask=None, dout=None, out=None):
+    """One layer of the relevance recursion for the row vector r [B, Ls] fp32, fused with the
+    recomputation of the attention probabilities from the layer's qkv buffer [B * Ls, 3, H, 64]
+    (fp32, bf16 or fp16, as attention_relevance takes it) in one launch that never writes the
+    [Ls, Ls] map (mmdx_token_relevance_step):
+
+        out[b, j] = alpha r[b, j] + beta sum_i r[b, i] abar[b, i, j]
+
+    with abar = mean_h P_h (dout=None) or mean_h relu(P_h * dP_h), dP_h = dO_h V_h^T (dout
+    [B * Ls, H, 64] in qkv's dtype), and P_h the softmax over the REAL keys: mask int64 [B, Ls],
+    1 = a real token (None: all real), the tensor the attention forward takes.  A masked key's
+    probability is exactly 0, so a masked column comes out as alpha r exactly; a sample without
+    a real key gives alpha r.  Bit-reproducible, row b independent of B.  1 <= Ls <= 256,
+    1 <= H <= 16.  A wrong dtype is a TypeError; a wrong shape, device or layout, a limit
+    exceeded, a non-finite scalar or an `out` that shares memory with an input is a ValueError;
+    nothing is copied or launched then."""
+    name = "token_relevance_step"
+    ops = (r, qkv) + tuple(t for t in (mask, dout) if t is not None)
+    if not all(torch.is_tensor(t) for t in ops):
+        raise TypeError(f"{name} takes tensors")
+    dt = L.dtype_code(qkv.dtype)
+    if r.dtype != torch.float32:
+        raise TypeError(f"{name}: r is {r.dtype}, not fp32")
+    if dout is not None and dout.dtype != qkv.dtype:
+        raise TypeError(f"{name}: dout is {dout.dtype}, qkv {qkv.dtype}")
+    if mask is not None and mask.dtype != torch.int64:
+        raise TypeError(f"{name}: mask is {mask.dtype}, not int64")
+    B, Ls, H = int(B), int(Ls), int(H)
+    if B < 1 or not 1 <= Ls <= ATTN_REL_MAX_L or not 1 <= H <= ATTN_REL_MAX_H:
+        raise ValueError(f"{name}: B = {B}, Ls = {Ls}, H = {H} outside B >= 1, 1 <= Ls <= "
+                         f"{ATTN_REL_MAX_L}, 1 <= H <= {ATTN_REL_MAX_H}")
+    if not all(np.isfinite(float(v)) for v in (scale, alpha, beta)):
+        raise ValueError(f"{name}: scale = {scale}, alpha = {alpha}, beta = {beta}")
+    if tuple(r.shape) != (B, Ls):
+        raise ValueError(f"{name}: r {tuple(r.shape)} is not [{B}, {Ls}]")
+    if mask is not None and tuple(mask.shape) != (B, Ls):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)} is not [{B}, {Ls}]")
+    if qkv.numel() != B * Ls * 3 * H * ATTN_REL_HD:
+        raise ValueError(f"{name}: qkv {tuple(qkv.shape)} is not [{B * Ls}, 3, {H}, "
+                         f"{ATTN_REL_HD}]")
+    if dout is not None and dout.numel() != B * Ls * H * ATTN_REL_HD:
+        raise ValueError(f"{name}: dout {tuple(dout.shape)} is not [{B * Ls}, {H}, "
+                         f"{ATTN_REL_HD}]")
+    out = _f32_out(name, out, (B, Ls), *ops)
+    ws, n = _token_workspace(B, Ls, r.device)
+    call("mmdx_token_relevance_step", dt, ptr(qkv), ptr(dout), ptr(mask), ptr(r), B, Ls, H,
+         float(scale), float(alpha), float(beta), ptr(out), ptr(ws), n, stream())
     return out
 
 

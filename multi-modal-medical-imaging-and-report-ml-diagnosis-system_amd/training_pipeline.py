@@ -286,6 +286,11 @@ class _HashWordTokenizer:
         return {"input_ids": ids, "token_type_ids": torch.zeros_like(ids),
                 "attention_mask": mask}
 
+    def token_strings(self, text_list, max_length=96):
+        """Per text, the strings of the real positions of __call__'s ids, in id order."""
+        return [["[CLS]"] + re.findall(r"\w+|[^\w\s]", t.lower())[: max_length - 2] + ["[SEP]"]
+                for t in text_list]
+
 
 class _WordPieceTokenizer:
     """bert-base-uncased's tokenizer (what AutoTokenizer builds at TP:323: BertTokenizerFast,
@@ -315,6 +320,12 @@ class _WordPieceTokenizer:
                 "attention_mask": torch.tensor([e.attention_mask for e in enc],
                                                dtype=torch.long)}
 
+    def token_strings(self, text_list, max_length=96):
+        """Per text, the encodings' tokens without the pads ("##" marks a continuation piece)."""
+        self.tok.enable_truncation(max_length)
+        self.tok.no_padding()
+        return [list(e.tokens) for e in self.tok.encode_batch(list(text_list))]
+
 
 def _tokenizer():
     if _TOKENIZER[0] is None:
@@ -329,6 +340,12 @@ def _tokenizer():
 def tokenize_patient_details(text_list, max_len=96):  # TP:335-342
     return _tokenizer()(text_list, padding="max_length", truncation=True, return_tensors="pt",
                         max_length=max_len)
+
+
+def token_strings(text_list, max_len=96):
+    """The token strings behind tokenize_patient_details(text_list, max_len): per text, those of
+    the real positions (attention_mask == 1) in id order, "[CLS]" and "[SEP]" included."""
+    return _tokenizer().token_strings(text_list, max_length=max_len)
 
 
 def _build_text_backbone(model_name):
