@@ -982,7 +982,26 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_kernel(
 //     P' and dS formed in registers, dV^T += dO^T P', dK^T += Q^T dS.
 // K (A) and Q, dO (B) are staged once per block as [LP][LDT] images: plain 16-B reads give
 // the S / dP operands, ds_read_b64_tr_b16 the transposed ones.
+// A fully padded batch row (every key masked) cannot be recomputed from its lse: the forward's
+// scores are all MASK_NEG (fp32 absorbs s * scale), so P = 1 / L on the keys < L, and the saved
+// lse = MASK_NEG + log L is MASK_NEG again; exp(score - lse) would give 1, L times the P that
+// the forward used and that attn_bwd_q16_kernel / attn_bwd_kv16_kernel read back.  Such a row
+// is a property of the batch row, hence of the whole block (head_fully_masked): the block then
+// takes scale = 0, lse = 0 and -log L as the key mask, so the same expression gives
+// exp(-log L) = 1 / L at no cost in the key loop.
 // ---------------------------------------------------------------------------------------
+// every row of head (b, h) has all of its keys masked: its lse is MASK_NEG, which no row with
+// an unmasked key comes near
+__device__ __forceinline__ bool head_fully_masked(const float* __restrict__ lse_head) {
+  return lse_head[0] <= 0.5f * MASK_NEG;
+}
+// the additive key mask of the recomputation: key_mask_add, or -log L on the keys of a fully
+// masked head
+__device__ __forceinline__ float key_mask_recompute(bool all_masked, const int64_t* mask, int b,
+                                                    int L, int key) {
+  if (!all_masked) return key_mask_add(mask, b, L, key);
+  return key < L ? -__logf((float)L) : -INFINITY;
+}
 template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
     const T* __restrict__ qkv, const T* __restrict__ outp, const float* __restrict__ lse,
@@ -1002,6 +1021,8 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
   const long orow = ((long)b * L + q) * H * HD + h * HD;
+  // (read first: the load then overlaps the row fragments' and the staging's)
+  const bool all_masked = head_fully_masked(lse + ((long)b * H + h) * L);
   F qf[2], of[2], ov[2];
   load_row_frags<T>(qf, base + (long)q * row_ld, q < L, g);
   load_row_frags<T>(of, dout + orow, q < L, g);
@@ -1014,11 +1035,13 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
   dot = column_sum(dot);
   stage_pair<T, 4, false, false>(Vs, LDR, base + 2L * H * HD, Ks, LDT, base + (long)H * HD,
                                  row_ld, LP, L, NW * 64);
-  for (int k = threadIdx.x; k < LP; k += NW * 64) madd[k] = key_mask_add(mask, b, L, k);
+  const float sc = all_masked ? 0.f : scale;   // the score's scale (dQ keeps `scale`)
+  for (int k = threadIdx.x; k < LP; k += NW * 64)
+    madd[k] = key_mask_recompute(all_masked, mask, b, L, k);
   __syncthreads();   // the only barrier
   if (at.idle) return;
   if (g == 0 && q < L) Dg[((long)b * H + h) * L + q] = dot;
-  const float lq = q < L ? lse[((long)b * H + h) * L + q] : 0.f;
+  const float lq = q < L && !all_masked ? lse[((long)b * H + h) * L + q] : 0.f;
   const HeadDropout dr(p_drop, p_drop > 0.f ? rng[0] : 0ull, b, h, H, L);
   f32x4 o[HD / 16];
   zero_tiles(o);
@@ -1036,7 +1059,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_q16_lse_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = j * 16 + g * 4 + r;
-        const float p = __expf(st[r] * scale + ma[r] - lq);
+        const float p = __expf(st[r] * sc + ma[r] - lq);
         const float dp = dr.keep(q, key) ? tp[r] * dr.keep_scale : 0.f;
         df[h2 * 4 + r] = from_f<T>(p * (dp - dot));
       }
@@ -1065,20 +1088,23 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_lse_kernel(
   const long row_ld = 3L * H * HD;
   const T* base = qkv + (long)b * L * row_ld + h * HD;
   const bool kok = key < L;
+  const long hq = ((long)b * H + h) * L;
+  // (read first: the load then overlaps the row fragments' and the staging's)
+  const bool all_masked = head_fully_masked(lse + hq);
   F kf[2], vf[2];
   load_row_frags<T>(kf, base + (long)key * row_ld + (long)H * HD, kok, g);
   load_row_frags<T>(vf, base + (long)key * row_ld + 2L * H * HD, kok, g);
   stage_rows<T, 4, false>(Qs, LDT, base, row_ld, LP, L, NW * 64);
   stage_rows<T, 4, false>(Os, LDT, dout + (long)b * L * H * HD + h * HD, (long)H * HD, LP, L,
                           NW * 64);
-  const long hq = ((long)b * H + h) * L;
+  const float sc = all_masked ? 0.f : scale;   // the score's scale (dK keeps `scale`)
   for (int i = threadIdx.x; i < LP; i += NW * 64) {
-    ls[i] = i < L ? lse[hq + i] : 0.f;
+    ls[i] = i < L && !all_masked ? lse[hq + i] : 0.f;
     ds_[i] = i < L ? Dg[hq + i] : 0.f;
   }
   __syncthreads();   // the only barrier
   if (at.idle) return;
-  const float mk = key_mask_add(mask, b, L, key);
+  const float mk = key_mask_recompute(all_masked, mask, b, L, key);
   const HeadDropout dr(p_drop, p_drop > 0.f ? rng[0] : 0ull, b, h, H, L);
   f32x4 dv[HD / 16], dk[HD / 16];
   zero_tiles(dv);
@@ -1095,7 +1121,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void attn_bwd_kv16_lse_kernel(
       const f32x4 dq = *(const f32x4*)(ds_ + qr0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = __expf(st[r] * scale + mk - lq[r]);
+        const float p = __expf(st[r] * sc + mk - lq[r]);
         const bool keep = dr.keep(qr0 + r, key);
         const float dp = keep ? tp[r] * dr.keep_scale : 0.f;
         pf[u * 4 + r] = from_f<T>(keep ? p * dr.keep_scale : 0.f);
