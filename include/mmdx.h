@@ -183,6 +183,21 @@ size_t mmdx_conv_wgrad_workspace_size(int dtype, const mmdx_conv_desc* d);
 int mmdx_conv_wgrad(int dtype, const mmdx_conv_desc* d, int c_master, const void* x,
                     const void* dy, float* dw_kcrs, float beta, void* workspace,
                     size_t ws_bytes, void* stream);
+/* Host only (no GPU needed): the kernel path a conv launch takes for this descriptor under the
+ * MMDX_* knobs in force, from the functions the launch itself calls.  pass 0: mmdx_conv_fwd
+ * (mmdx_conv_fwd_bn_eval takes the same path, except that it never runs the direct stem
+ * kernel); 1: mmdx_conv_dgrad with this beta (it decides which phases of a strided conv are
+ * launched); 2: mmdx_conv_wgrad.  dtype: MMDX_F32 | MMDX_BF16.
+ *   fwd, stride-1 dgrad: "<operand>/<loader>/<tile>[/ns<stages>]", operand point | fast |
+ *     generic, loader kload | dma | dma-lanetap, tile 128x64 | 128x128 | 128x128-8w | 256x64;
+ *     the stage count where the grid rule picks it (the 4-wave LDS-DMA tiles).
+ *   strided dgrad: "phases-merged/dma/<tile>" | "phases-each/kload/<tile>".
+ *   wgrad: "<bm>x<bn>/<operand>[/ns<stages>]/<reduction>/s<splits>/k<kper>", operand DmaRq |
+ *     DmaR | DmaR-point | RLoad, reduction reduce | reduce-z, kper the pixels of one split.
+ *   the direct pixel-pair stem kernels: "stem-direct" (fwd), "stem-direct/<reduction>/s../k..".
+ * Writes a NUL-terminated string of fewer than n bytes to out. */
+int mmdx_conv_describe(int dtype, int pass, const mmdx_conv_desc* d, float beta, char* out,
+                       size_t n);
 
 /* ResNet stem (backbone.0, TP:183: 7x7 / stride 2 / pad 3 over the 3-channel image) as an
  * ordinary conv over PIXEL PAIRS (bf16 path): the NCHW fp32 batch of

@@ -95,6 +95,7 @@ SIGNATURES = {
     "mmdx_conv_dgrad_accmask": (i32, [i32, CD, vp, vp, vp, vp, vp, vp]),
     "mmdx_conv_wgrad_workspace_size": (sz, [i32, CD]),
     "mmdx_conv_wgrad": (i32, [i32, CD, i32, vp, vp, vp, f32, vp, sz, vp]),
+    "mmdx_conv_describe": (i32, [i32, i32, CD, f32, C.c_char_p, sz]),
     "mmdx_stem_pair_desc": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, CD]),
     "mmdx_stem_pair_input": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "mmdx_stem_pair_pack_weight": (i32, [vp, i32, i32, i32, i32, vp, vp]),

@@ -175,15 +175,16 @@ __global__ __launch_bounds__(256) void wgrad_reduce_z_kernel(const float* __rest
   }
 }
 
+// Split groups (wgrad_reduce_z_kernel) only for the deep splits (>= 128: the stem's and
+// layer1's weight gradients, at the end of the backward where little else runs); elsewhere the
+// per-element loop, whose lower memory-level parallelism disturbs the concurrent dgrad/BN chain
+// less (all-split: 0.6 % slower train step despite 2 % less isolated wgrad time).
+static bool wgrad_reduce_z(int splits, long total) { return total % 4 == 0 && splits >= 128; }
+
 static void wgrad_reduce(const float* ws, int splits, int K, int C, int Cm, int RS, float* dw,
                          float beta, hipStream_t st) {
   const long total = (long)K * C * RS;  // < 2^31: checked by the wgrad entry point
-  // split groups only for the deep splits (>= 128: the stem's and layer1's weight gradients,
-  // at the end of the backward where little else runs); elsewhere the per-element loop, whose
-  // lower memory-level parallelism disturbs the concurrent dgrad/BN chain less (all-split:
-  // 0.6 % slower train step despite 2 % less isolated wgrad time).
-  const bool per_element = splits < 128;
-  if (total % 4 != 0 || per_element) {
+  if (!wgrad_reduce_z(splits, total)) {
     const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, ws, splits, K, C,
                        Cm, RS, dw, beta);
@@ -223,34 +224,22 @@ static bool use_three_stages(long blocks, int ktiles_per_block) {
   return blocks <= 256 && ktiles_per_block >= 4;
 }
 
-template <int BM, int BN, class OA, class OB, class Epi, int NS>
-static void launch_dma_ns(const typename OA::SrcT& sa, const typename OB::SrcT& sb,
-                          const Epi& epi, int M, int N, int K, int splits, int kper, int nwg,
-                          hipStream_t st) {
-  hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, OA, OB, Epi, NS>), dim3(nwg, 1, splits),
-                     dim3(NT), 0, st, sa, sb, epi, M, N, K, kper);
-}
-
-template <int BM, int BN, class OA, class OB, class Epi>
-static int launch_dma_ops(const typename OA::SrcT& sa, const typename OB::SrcT& sb,
+// the 4-wave LDS-DMA kernel with the ns (2 | 3) operand stages the pass's path function chose;
+// MAXNS 2: the operands have no three-stage instantiation
+template <int BM, int BN, class OA, class OB, int MAXNS = 3, class Epi>
+static int launch_dma_ops(int ns, const typename OA::SrcT& sa, const typename OB::SrcT& sb,
                           const Epi& epi, int M, int N, int K, int splits, int kper,
                           hipStream_t st) {
-  const int nwg = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  if (use_three_stages((long)nwg * splits, (kper + 63) / 64)) {
-    launch_dma_ns<BM, BN, OA, OB, Epi, 3>(sa, sb, epi, M, N, K, splits, kper, nwg, st);
+  const dim3 grid(((M + BM - 1) / BM) * ((N + BN - 1) / BN), 1, splits);
+  if (MAXNS == 3 && ns == 3) {
+    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, OA, OB, Epi, MAXNS>), grid, dim3(NT), 0, st, sa,
+                       sb, epi, M, N, K, kper);
   } else {
-    launch_dma_ns<BM, BN, OA, OB, Epi, 2>(sa, sb, epi, M, N, K, splits, kper, nwg, st);
+    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, OA, OB, Epi, 2>), grid, dim3(NT), 0, st, sa, sb,
+                       epi, M, N, K, kper);
   }
   MMDX_LAUNCH_CHECK();
   return 0;
-}
-
-// both operands k-major
-template <int BM, int BN, class SA, class SB, class Epi>
-static int launch_dma(const SA& sa, const SB& sb, const Epi& epi, int M, int N, int K,
-                      int splits, int kper, hipStream_t st) {
-  return launch_dma_ops<BM, BN, DmaK<BM, SA>, DmaK<BN, SB>>(sa, sb, epi, M, N, K, splits, kper,
-                                                            st);
 }
 
 // bf16 gathers whose K tiles are whole filter taps (C % 64 == 0) take the LDS-DMA kernel
@@ -308,52 +297,104 @@ static bool conv_8w128_on() { return knobs().conv_8w128; }
 // weight-gradient tiles (MMDX_WGRAD_TAP_BN) and the BN finalize fused into the conv
 // (MMDX_BN_FIN, mmdx_conv_fwd_bnfin).
 
-template <typename T, class SA, class Epi>
-static int conv_gemm_epi(const SA& sa, const void* w, const Epi& epi, int M, int N, int K,
-                         hipStream_t st, bool dma_ok) {
-  DenseK<T> sb{(const T*)w, K, N, true};
-  if constexpr (DmaOk<SA>::value) {
-    if (dma_ok) {
-      // 128x64 tiles when N is narrow or 128x128 tiles would leave CUs idle (< 1.5 per CU)
-      const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-      if (N <= 64 && conv_n64_wide(M)) {
-        hipLaunchKernelGGL((igemm_dma_kernel<256, 64, DmaK<256, SA, 64, 8>,
-                                             DmaK<64, DenseK<T>, 64, 8>, Epi, 2, bf16, 512, 4, 2>),
-                           dim3((M + 255) / 256), dim3(512), 0, st, sa, sb, epi, M, N, K, K);
-        MMDX_LAUNCH_CHECK();
-        return 0;
-      }
-      if (N <= 64 || tiles128 < kNarrowBelow)
-        return launch_dma<128, 64>(sa, sb, epi, M, N, K, 1, K, st);
-      if (conv_8w128_on()) {
+// Dispatch.  The kernel a forward or a data gradient launches, decided on the host from the
+// element size, the geometry, what the caller fixes and knobs() alone: conv_fwd_path() and
+// conv_dgrad_path() name it, the launch code instantiates what they name and
+// mmdx_conv_describe() prints it, so the three cannot drift (the wgrad: conv_wgrad_path).
+enum ConvFamily {  // the A operand: Point*K (x or dY itself is the dense [M][K] operand) |
+                   // Im2colK / DgradK <true> (K tiles are whole taps) | <false> | DgradPhaseK in
+                   // one launch (grid z = phase) | per phase | stem_direct_fwd_kernel
+  FAM_POINT = 0, FAM_FAST, FAM_GENERIC, FAM_PHASES_MERGED, FAM_PHASES_EACH, FAM_STEM_DIRECT };
+enum ConvLoader { LOAD_KLOAD = 0, LOAD_DMA, LOAD_DMA_LANETAP };  // igemm_kernel | igemm_dma_kernel
+enum ConvTile { TILE_128x64 = 0, TILE_128x128, TILE_128x128_8W, TILE_256x64 };
+struct ConvPath {
+  int family, loader, tile;
+  int ns;  // operand stages of the LDS-DMA kernel; 0: the kernel has no such argument
+};
+
+// 128x64 tiles when N is narrow or 128x128 tiles would leave CUs idle (< 1.5 per CU)
+static bool narrow_tile(int N, long tiles128) { return N <= 64 || tiles128 < kNarrowBelow; }
+
+// loader, tile and stages of a k-major conv GEMM [M, N, K] (forward, stride-1 dgrad).  Only the
+// two 4-wave tiles consult use_three_stages, each with its own tile's block count; the KLoad
+// fallback picks its tile by N alone.
+static void kmajor_tile(ConvPath& p, bool dma, bool lane_tap, int M, int N, int K) {
+  const long m128 = (M + 127) / 128, tiles128 = m128 * ((N + 127) / 128);
+  p.loader = !dma ? LOAD_KLOAD : lane_tap ? LOAD_DMA_LANETAP : LOAD_DMA;
+  p.ns = dma ? 2 : 0;
+  if (!dma) p.tile = N <= 64 ? TILE_128x64 : TILE_128x128;
+  else if (N <= 64 && conv_n64_wide(M)) p.tile = TILE_256x64;
+  else if (narrow_tile(N, tiles128)) p.tile = TILE_128x64;
+  else p.tile = conv_8w128_on() ? TILE_128x128_8W : TILE_128x128;
+  const long blocks = p.tile == TILE_128x64 ? m128 * ((N + 63) / 64) : tiles128;
+  if (dma && p.tile <= TILE_128x128 && use_three_stages(blocks, (K + 63) / 64)) p.ns = 3;
+}
+
+// point | fast | generic by the channel count `red` the GEMM reduces over (C forward, K dgrad)
+static int kmajor_family(int esize, int red, const ConvGeom& g) {
+  const int BK = esize == 2 ? KTile<bf16>::BK : KTile<float>::BK;
+  return red % BK != 0 ? FAM_GENERIC : is_pointwise(g) ? FAM_POINT : FAM_FAST;
+}
+
+// The LDS-DMA launch a path names, both operands k-major; grid z = nz (the merged phases: nz
+// phases of up to M rows, K deep; they exist in the two 4-wave tiles with two stages only)
+template <class SA, class SB, class Epi>
+static int launch_kmajor_dma(const ConvPath& p, const SA& sa, const SB& sb, const Epi& epi,
+                             int M, int N, int K, int nz, hipStream_t st) {
+  constexpr bool kPhases = std::is_same<SA, DgradPhaseK<bf16>>::value;
+  if constexpr (!kPhases) {
+    if (p.tile == TILE_256x64 || p.tile == TILE_128x128_8W) {  // 8 waves of 64 x 32
+      if (p.tile == TILE_256x64)
+        hipLaunchKernelGGL((igemm_dma_kernel<256, 64, DmaK<256, SA, 64, 8>, DmaK<64, SB, 64, 8>,
+                                             Epi, 2, bf16, 512, 4, 2>),
+                           dim3((M + 255) / 256, 1, nz), dim3(512), 0, st, sa, sb, epi, M, N, K, K);
+      else
         hipLaunchKernelGGL((igemm_dma_kernel<128, 128, DmaK<128, SA, 64, 8>,
-                                             DmaK<128, DenseK<T>, 64, 8>, Epi, 2, bf16, 512, 2,
-                                             4>),
-                           dim3((unsigned)tiles128), dim3(512), 0, st, sa, sb, epi, M, N, K, K);
-        MMDX_LAUNCH_CHECK();
-        return 0;
-      }
-      return launch_dma<128, 128>(sa, sb, epi, M, N, K, 1, K, st);
+                                             DmaK<128, SB, 64, 8>, Epi, 2, bf16, 512, 2, 4>),
+                           dim3(((M + 127) / 128) * ((N + 127) / 128), 1, nz), dim3(512), 0, st,
+                           sa, sb, epi, M, N, K, K);
+      MMDX_LAUNCH_CHECK();
+      return 0;
     }
   }
-  if (N <= 64)
-    return launch<T, 128, 64, KLoad<T, 128, SA>, KLoad<T, 64, DenseK<T>>>(sa, sb, epi, M, N, K,
-                                                                            1, K, st);
-  return launch<T, 128, 128, KLoad<T, 128, SA>, KLoad<T, 128, DenseK<T>>>(sa, sb, epi, M, N, K,
-                                                                            1, K, st);
+  if (p.tile == TILE_128x64)
+    return launch_dma_ops<128, 64, DmaK<128, SA>, DmaK<64, SB>, kPhases ? 2 : 3>(
+        p.ns, sa, sb, epi, M, N, K, nz, K, st);
+  return launch_dma_ops<128, 128, DmaK<128, SA>, DmaK<128, SB>, kPhases ? 2 : 3>(
+      p.ns, sa, sb, epi, M, N, K, nz, K, st);
+}
+
+// the register-staged launch a path names, both operands k-major
+template <typename T, class SA, class SB, class Epi>
+static int launch_kmajor_kload(const ConvPath& p, const SA& sa, const SB& sb, const Epi& epi,
+                               int M, int N, int K, hipStream_t st) {
+  MMDX_CHECK_ARG(p.loader == LOAD_KLOAD, "conv: no LDS-DMA kernel for this operand");
+  if (p.tile == TILE_128x64)
+    return launch<T, 128, 64, KLoad<T, 128, SA>, KLoad<T, 64, SB>>(sa, sb, epi, M, N, K, 1, K, st);
+  return launch<T, 128, 128, KLoad<T, 128, SA>, KLoad<T, 128, SB>>(sa, sb, epi, M, N, K, 1, K, st);
+}
+
+template <typename T, class SA, class Epi>
+static int conv_gemm_epi(const ConvPath& p, const SA& sa, const void* w, const Epi& epi, int M,
+                         int N, int K, hipStream_t st) {
+  DenseK<T> sb{(const T*)w, K, N, true};
+  if constexpr (DmaOk<SA>::value) {
+    if (p.loader != LOAD_KLOAD) return launch_kmajor_dma(p, sa, sb, epi, M, N, K, 1, st);
+  }
+  return launch_kmajor_kload<T>(p, sa, sb, epi, M, N, K, st);
 }
 
 template <typename T, class SA>
-static int conv_gemm(const SA& sa, const void* w, void* out, int M, int N, int K, float beta,
-                     hipStream_t st, float* stats = nullptr, bool dma_ok = false,
+static int conv_gemm(const ConvPath& p, const SA& sa, const void* w, void* out, int M, int N,
+                     int K, float beta, hipStream_t st, float* stats = nullptr,
                      const BnStat& bs = BnStat{}, const void* acc_src = nullptr,
                      const uint8_t* acc_mask = nullptr) {
   EpiStore<T> epi{(T*)out, N, M, N, nullptr, nullptr, ACT_NONE, 1.f, beta, nullptr,
                   (float2*)stats};
-  epi.bs = bs;  // only the LDS-DMA kernel's epilogue honours it (see dgrad_bnstat_ok)
+  epi.bs = bs;  // only the LDS-DMA kernel's epilogue honours it (mmdx_conv_dgrad_stat_blocks)
   epi.acc_src = (const T*)acc_src;
   epi.acc_mask = acc_mask;
-  return conv_gemm_epi<T>(sa, w, epi, M, N, K, st, dma_ok);
+  return conv_gemm_epi<T>(p, sa, w, epi, M, N, K, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -485,6 +526,34 @@ static int stem_direct_fwd(const ConvGeom& g, const void* x, const void* w, void
   return 0;
 }
 
+// channel count a power of two: the LDS-DMA kernel decodes each lane's tap itself
+static bool lane_tap_geom(const ConvGeom& g) {
+  return g.C >= 8 && (g.C & (g.C - 1)) == 0 && g.R * g.S <= 64;
+}
+
+// direct: the caller asked for the direct stem kernel (conv_fwd_t: by the statistics slab size
+// or the knob; mmdx_conv_fwd_bn_eval never does).  fp32 never takes the LDS-DMA kernels.
+static ConvPath conv_fwd_path(int esize, const ConvGeom& g, bool direct) {
+  if (direct && esize == 2 && stem_direct_geom(g)) return ConvPath{FAM_STEM_DIRECT, 0, 0, 0};
+  const int M = g.N * g.P * g.Q;
+  ConvPath p{kmajor_family(esize, g.C, g), 0, 0, 0};
+  const bool generic = p.family == FAM_GENERIC;  // DMA then needs its 64-tap mask
+  const bool dma = esize == 2 && (!generic || lane_tap_geom(g)) &&
+                   dma_geom_ok(g, false, generic ? 64 : 32, M);
+  kmajor_tile(p, dma, generic, M, g.K, g.R * g.S * g.C);
+  return p;
+}
+
+// builds the A operand the path's family names and hands it to f
+template <typename T, class F>
+static int with_fwd_operand(const ConvPath& p, const ConvGeom& g, const void* x, int M, F&& f) {
+  if (p.family == FAM_POINT)  // x itself is the [M][C] A operand
+    return f(PointFwdK<T>{{(const T*)x, g.C, M, true}});
+  if (p.family == FAM_FAST) return f(Im2colK<T, true>{(const T*)x, g, M});
+  return f(Im2colK<T, false>{(const T*)x, g, M, lane_tap_geom(g) ? __builtin_ctz(g.C) : 0,
+                             1.f / (float)g.S});
+}
+
 // stat_rows: the rows per statistics slab the caller sized `stats` for (128; 2*Q selects the
 // direct stem kernel, which writes one slab per block); without stats the knob decides
 template <typename T>
@@ -492,24 +561,17 @@ static int conv_fwd_t(const mmdx_conv_desc* d, const void* x, const void* w, voi
                       float* stats, int stat_rows, hipStream_t st) {
   const ConvGeom g = geom(d);
   const int M = g.N * g.P * g.Q, N = g.K, K = g.R * g.S * g.C;
-  const bool direct = stem_direct_geom(g) && std::is_same<T, bf16>::value &&
-                      (stats ? stat_rows == STEM_PB * g.Q : stem_direct_on());
+  const ConvPath p = conv_fwd_path((int)sizeof(T), g,
+                                   stats ? stat_rows == STEM_PB * g.Q : stem_direct_on());
+  const bool direct = p.family == FAM_STEM_DIRECT;
   MMDX_CHECK_ARG(!stats || direct || stat_rows == 128,
                  "conv fwd: statistics slabs of %d rows (128, or %d for the direct stem)",
                  stat_rows, STEM_PB * g.Q);
   if constexpr (std::is_same<T, bf16>::value)
     if (direct) return stem_direct_fwd(g, x, w, y, stats, st);
-  if (g.C % KTile<T>::BK == 0 && is_pointwise(g))  // x itself is the [M][C] A operand
-    return conv_gemm<T>(PointFwdK<T>{{(const T*)x, g.C, M, true}}, w, y, M, N, K, 0.f, st,
-                        stats, dma_geom_ok(g, false, 32, M));
-  if (g.C % KTile<T>::BK == 0)
-    return conv_gemm<T>(Im2colK<T, true>{(const T*)x, g, M}, w, y, M, N, K, 0.f, st, stats,
-                        dma_geom_ok(g, false, 32, M));
-  // channel count a power of two: the LDS-DMA kernel decodes each lane's tap itself
-  const bool pow2 = g.C >= 8 && (g.C & (g.C - 1)) == 0 && g.R * g.S <= 64;
-  Im2colK<T, false> sa{(const T*)x, g, M, pow2 ? __builtin_ctz(g.C) : 0, 1.f / (float)g.S};
-  return conv_gemm<T>(sa, w, y, M, N, K, 0.f, st, stats, pow2 && dma_geom_ok(g, false, 64, M),
-                      BnStat{});
+  return with_fwd_operand<T>(p, g, x, M, [&](const auto& sa) {
+    return conv_gemm<T>(p, sa, w, y, M, N, K, 0.f, st, stats);
+  });
 }
 
 template <typename T>
@@ -524,19 +586,13 @@ static int conv_fwd_bn_eval_t(const mmdx_conv_desc* d, const void* x, const void
       EpiStore<T>{(T*)y, N, M, N, nullptr, nullptr, ACT_NONE, 1.f, 0.f, nullptr, nullptr};
   epi.gamma = gamma; epi.beta_bn = beta; epi.rmean = rmean; epi.rvar = rvar; epi.eps = eps;
   epi.res = (const T*)res; epi.relu = relu != 0;
-  if (g.C % KTile<T>::BK == 0 && is_pointwise(g))
-    return conv_gemm_epi<T>(PointFwdK<T>{{(const T*)x, g.C, M, true}}, w, epi, M, N, K, st,
-                            dma_geom_ok(g, false, 32, M));
-  if (g.C % KTile<T>::BK == 0)
-    return conv_gemm_epi<T>(Im2colK<T, true>{(const T*)x, g, M}, w, epi, M, N, K, st,
-                            dma_geom_ok(g, false, 32, M));
-  const bool pow2 = g.C >= 8 && (g.C & (g.C - 1)) == 0 && g.R * g.S <= 64;
-  Im2colK<T, false> sa{(const T*)x, g, M, pow2 ? __builtin_ctz(g.C) : 0, 1.f / (float)g.S};
-  return conv_gemm_epi<T>(sa, w, epi, M, N, K, st, pow2 && dma_geom_ok(g, false, 64, M));
+  const ConvPath p = conv_fwd_path((int)sizeof(T), g, false);
+  return with_fwd_operand<T>(p, g, x, M, [&](const auto& sa) {
+    return conv_gemm_epi<T>(p, sa, w, epi, M, N, K, st);
+  });
 }
 
-// Strided dgrad as sh*sw phase GEMMs (see DgradPhaseK); phases no tap reaches are written
-// as zeros (beta = 0) or left untouched (beta != 0).
+// the geometry of phase (a, b) of a strided dgrad; false: the phase has no pixels
 static bool phase_geom(const ConvGeom& g, int a, int b, PhaseGeom& ph) {
   ph.Hp = g.H > a ? (g.H - a + g.sh - 1) / g.sh : 0;
   ph.Wp = g.W > b ? (g.W - b + g.sw - 1) / g.sw : 0;
@@ -550,29 +606,59 @@ static bool phase_geom(const ConvGeom& g, int a, int b, PhaseGeom& ph) {
   return true;
 }
 
-// bf16 LDS-DMA path: every phase in ONE launch (grid z = phase; each block selects its own
-// phase's geometry, EpiPhase::select).  The sh*sw separate launches each filled a quarter of
-// the chip (layer4's 3x3/2: 4 x 196 tiles of 128 x 128 on 256 CUs) and were the slowest
-// C4 convs per FLOP (isolated 0.175-0.186 of their roofline).
-template <typename T>
-static int conv_dgrad_phases_merged(const ConvGeom& g, const void* dy, const void* w_crsk,
-                                    void* dx, float beta, hipStream_t st, BnStat bs) {
-  DgradPhaseK<T> sa{(const T*)dy, g, PhaseGeom{}, 0};
-  PhaseTapK<T> sb{(const T*)w_crsk, (long)g.R * g.S * g.K, g.C, g.K, g.S, g.sh, g.sw,
-                  PhaseGeom{}};
-  EpiPhase<T> epi{(T*)dx, g.C, 0, g.C, beta, 0, 0, g.H, g.W, 0, 0, g.sh, g.sw};
-  epi.bs = bs;
-  const int N = g.C;
-  int np = 0, mmax = 0, kmax = 0;
-  long tiles128 = 0;
+// f(a, b, ph, M, K) for every phase a strided dgrad launches, in launch order: phases no tap
+// reaches (K == 0) are written as zeros at beta 0 and left out of the grid otherwise
+template <class F>
+static void for_each_phase(const ConvGeom& g, float beta, F&& f) {
   for (int a = 0; a < g.sh; ++a) {
     for (int b = 0; b < g.sw; ++b) {
       PhaseGeom ph;
       if (!phase_geom(g, a, b, ph)) continue;
       const int K = ph.ntr * ph.nts * g.K;
       if (K == 0 && beta != 0.f) continue;
-      MMDX_CHECK_ARG(np < MAX_PHASES, "dgrad phases: more than %d", MAX_PHASES);
-      const int M = g.N * ph.Hp * ph.Wp;
+      f(a, b, ph, g.N * ph.Hp * ph.Wp, K);
+    }
+  }
+}
+
+// beta decides which phases are launched, and so the merged grid's tile count.  The generic
+// dgrad (K % BK != 0) has no LDS-DMA kernel, and fp32 never takes one.
+static ConvPath conv_dgrad_path(int esize, const ConvGeom& g, float beta) {
+  const int BK = esize == 2 ? KTile<bf16>::BK : KTile<float>::BK, N = g.C;
+  if ((g.sh > 1 || g.sw > 1) && g.K % BK == 0) {
+    const long rows = (long)g.N * ((g.H + g.sh - 1) / g.sh) * ((g.W + g.sw - 1) / g.sw);
+    if (esize != 2 || !dma_geom_ok(g, false, 32, rows))
+      return ConvPath{FAM_PHASES_EACH, LOAD_KLOAD, N <= 64 ? TILE_128x64 : TILE_128x128, 0};
+    long tiles128 = 0;  // the 128x64 / 128x128 choice on the whole grid's tiles; two stages
+    for_each_phase(g, beta, [&](int, int, const PhaseGeom&, int M, int) {
+      tiles128 += (long)((M + 127) / 128) * ((N + 127) / 128);
+    });
+    return ConvPath{FAM_PHASES_MERGED, LOAD_DMA,
+                    narrow_tile(N, tiles128) ? TILE_128x64 : TILE_128x128, 2};
+  }
+  const int M = g.N * g.H * g.W;
+  ConvPath p{kmajor_family(esize, g.K, g), 0, 0, 0};
+  const bool dma = esize == 2 && p.family != FAM_GENERIC && dma_geom_ok(g, true, 32, M);
+  kmajor_tile(p, dma, false, M, N, g.R * g.S * g.K);
+  return p;
+}
+
+// bf16 LDS-DMA path: every phase in ONE launch (grid z = phase; each block selects its own
+// phase's geometry, EpiPhase::select).  The sh*sw separate launches each filled a quarter of
+// the chip (layer4's 3x3/2: 4 x 196 tiles of 128 x 128 on 256 CUs) and were the slowest
+// C4 convs per FLOP (isolated 0.175-0.186 of their roofline).
+template <typename T>
+static int conv_dgrad_phases_merged(const ConvPath& p, const ConvGeom& g, const void* dy,
+                                    const void* w_crsk, void* dx, float beta, hipStream_t st,
+                                    BnStat bs) {
+  DgradPhaseK<T> sa{(const T*)dy, g, PhaseGeom{}, 0};
+  PhaseTapK<T> sb{(const T*)w_crsk, (long)g.R * g.S * g.K, g.C, g.K, g.S, g.sh, g.sw,
+                  PhaseGeom{}};
+  EpiPhase<T> epi{(T*)dx, g.C, 0, g.C, beta, 0, 0, g.H, g.W, 0, 0, g.sh, g.sw};
+  epi.bs = bs;
+  int np = 0, mmax = 0, kmax = 0;
+  for_each_phase(g, beta, [&](int a, int b, const PhaseGeom& ph, int M, int K) {
+    if (np < MAX_PHASES) {
       sa.phs[np] = sb.phs[np] = ph;
       sa.Ms[np] = epi.Ms[np] = M;
       epi.Ks[np] = K;
@@ -582,59 +668,40 @@ static int conv_dgrad_phases_merged(const ConvGeom& g, const void* dy, const voi
       bs.tile0 += (M + 127) / 128;  // the next phase's statistics tiles follow this phase's
       mmax = std::max(mmax, M);
       kmax = std::max(kmax, K);
-      tiles128 += (long)((M + 127) / 128) * ((N + 127) / 128);
-      ++np;
     }
-  }
+    ++np;
+  });
+  MMDX_CHECK_ARG(np <= MAX_PHASES, "dgrad phases: more than %d", MAX_PHASES);
   if (np == 0) return 0;
-  // the 128x64 / 128x128 choice on the whole grid's tiles
-  if (N <= 64 || tiles128 < kNarrowBelow) {
-    const int nwg = ((mmax + 127) / 128) * ((N + 63) / 64);
-    hipLaunchKernelGGL((igemm_dma_kernel<128, 64, DmaK<128, DgradPhaseK<T>>,
-                                         DmaK<64, PhaseTapK<T>>, EpiPhase<T>, 2>),
-                       dim3(nwg, 1, np), dim3(NT), 0, st, sa, sb, epi, mmax, N, kmax, kmax);
-  } else {
-    const int nwg = ((mmax + 127) / 128) * ((N + 127) / 128);
-    hipLaunchKernelGGL((igemm_dma_kernel<128, 128, DmaK<128, DgradPhaseK<T>>,
-                                         DmaK<128, PhaseTapK<T>>, EpiPhase<T>, 2>),
-                       dim3(nwg, 1, np), dim3(NT), 0, st, sa, sb, epi, mmax, N, kmax, kmax);
-  }
-  MMDX_LAUNCH_CHECK();
-  return 0;
+  return launch_kmajor_dma(p, sa, sb, epi, mmax, g.C, kmax, np, st);
 }
 
+// Strided dgrad as one launch per phase (see DgradPhaseK)
 template <typename T>
-static int conv_dgrad_phases(const ConvGeom& g, const void* dy, const void* w_crsk, void* dx,
-                             float beta, hipStream_t st, BnStat bs = BnStat{}) {
-  if constexpr (sizeof(T) == 2) {
-    if (dma_geom_ok(g, false, 32, (long)g.N * ((g.H + g.sh - 1) / g.sh) *
-                                       ((g.W + g.sw - 1) / g.sw)))
-      return conv_dgrad_phases_merged<T>(g, dy, w_crsk, dx, beta, st, bs);
-  }
-  for (int a = 0; a < g.sh; ++a) {
-    for (int b = 0; b < g.sw; ++b) {
-      PhaseGeom ph;
-      if (!phase_geom(g, a, b, ph)) continue;
-      const int K = ph.ntr * ph.nts * g.K;
-      if (K == 0 && beta != 0.f) continue;
-      const int M = g.N * ph.Hp * ph.Wp, N = g.C;
-      DgradPhaseK<T> sa{(const T*)dy, g, ph, M};
-      PhaseTapK<T> sb{(const T*)w_crsk, (long)g.R * g.S * g.K, g.C, g.K, g.S, g.sh, g.sw, ph};
-      EpiPhase<T> epi{(T*)dx, g.C, M, N, beta, ph.Hp, ph.Wp, g.H, g.W, a, b, g.sh, g.sw};
-      epi.bs = bs;
-      bs.tile0 += (M + 127) / 128;  // the next phase's tiles follow this phase's
-      int rc = -1;
-      if (N <= 64) {
-        rc = launch<T, 128, 64, KLoad<T, 128, DgradPhaseK<T>>, KLoad<T, 64, PhaseTapK<T>>>(
-            sa, sb, epi, M, N, K, 1, K, st);
-      } else {
-        rc = launch<T, 128, 128, KLoad<T, 128, DgradPhaseK<T>>, KLoad<T, 128, PhaseTapK<T>>>(
-            sa, sb, epi, M, N, K, 1, K, st);
-      }
-      if (rc) return rc;
-    }
-  }
-  return 0;
+static int conv_dgrad_phases_each(const ConvPath& p, const ConvGeom& g, const void* dy,
+                                  const void* w_crsk, void* dx, float beta, hipStream_t st,
+                                  BnStat bs) {
+  int rc = 0;
+  for_each_phase(g, beta, [&](int a, int b, const PhaseGeom& ph, int M, int K) {
+    if (rc) return;
+    DgradPhaseK<T> sa{(const T*)dy, g, ph, M};
+    PhaseTapK<T> sb{(const T*)w_crsk, (long)g.R * g.S * g.K, g.C, g.K, g.S, g.sh, g.sw, ph};
+    EpiPhase<T> epi{(T*)dx, g.C, M, g.C, beta, ph.Hp, ph.Wp, g.H, g.W, a, b, g.sh, g.sw};
+    epi.bs = bs;
+    bs.tile0 += (M + 127) / 128;  // the next phase's tiles follow this phase's
+    rc = launch_kmajor_kload<T>(p, sa, sb, epi, M, g.C, K, st);
+  });
+  return rc;
+}
+
+// builds the A operand the path's family names and hands it to f
+template <typename T, class F>
+static int with_dgrad_operand(const ConvPath& p, const ConvGeom& g, const void* dy, int M,
+                              F&& f) {
+  if (p.family == FAM_POINT)  // dY itself is the [M][K] A operand
+    return f(PointDgradK<T>{{(const T*)dy, g.K, M, true}});
+  if (p.family == FAM_FAST) return f(DgradK<T, true>{(const T*)dy, g, M});
+  return f(DgradK<T, false>{(const T*)dy, g, M});
 }
 
 template <typename T>
@@ -642,17 +709,16 @@ static int conv_dgrad_t(const mmdx_conv_desc* d, const void* dy, const void* w_c
                         float beta, hipStream_t st, const BnStat& bs = BnStat{},
                         const void* acc_src = nullptr, const uint8_t* acc_mask = nullptr) {
   const ConvGeom g = geom(d);
-  if ((g.sh > 1 || g.sw > 1) && g.K % KTile<T>::BK == 0)
-    return conv_dgrad_phases<T>(g, dy, w_crsk, dx, beta, st, bs);
+  const ConvPath p = conv_dgrad_path((int)sizeof(T), g, beta);
+  if constexpr (sizeof(T) == 2)
+    if (p.family == FAM_PHASES_MERGED)
+      return conv_dgrad_phases_merged<T>(p, g, dy, w_crsk, dx, beta, st, bs);
+  if (p.family == FAM_PHASES_EACH)
+    return conv_dgrad_phases_each<T>(p, g, dy, w_crsk, dx, beta, st, bs);
   const int M = g.N * g.H * g.W, N = g.C, K = g.R * g.S * g.K;
-  if (g.K % KTile<T>::BK == 0 && is_pointwise(g))  // dY itself is the [M][K] A operand
-    return conv_gemm<T>(PointDgradK<T>{{(const T*)dy, g.K, M, true}}, w_crsk, dx, M, N, K,
-                        beta, st, nullptr, dma_geom_ok(g, true, 32, M), bs, acc_src, acc_mask);
-  if (g.K % KTile<T>::BK == 0)
-    return conv_gemm<T>(DgradK<T, true>{(const T*)dy, g, M}, w_crsk, dx, M, N, K, beta, st,
-                        nullptr, dma_geom_ok(g, true, 32, M), bs, acc_src, acc_mask);
-  return conv_gemm<T>(DgradK<T, false>{(const T*)dy, g, M}, w_crsk, dx, M, N, K, beta, st,
-                      nullptr, false, BnStat{}, acc_src, acc_mask);
+  return with_dgrad_operand<T>(p, g, dy, M, [&](const auto& sa) {
+    return conv_gemm<T>(p, sa, w_crsk, dx, M, N, K, beta, st, nullptr, bs, acc_src, acc_mask);
+  });
 }
 
 struct WgradPlan { int bm, bn, splits, kper; };
@@ -663,17 +729,17 @@ struct WgradPlan { int bm, bn, splits, kper; };
 // 768 / 1024 -0.6 / -0.8 %; conv HBM traffic 145.2 -> 137.7 MB per launch (fewer fp32 slabs)
 static long wgrad_split_target() { return knobs().wgrad_target; }
 
-static WgradPlan plan_wgrad(int dtype, const mmdx_conv_desc* d) {
+static WgradPlan plan_wgrad(int esize, const ConvGeom& g) {
   WgradPlan p;
-  const int BK = dtype == BF16 ? KTile<bf16>::BK : KTile<float>::BK;
-  const int M = d->K, N = d->R * d->S * d->C;
-  const long K = (long)d->N * d->P * d->Q;
+  const int BK = esize == 2 ? KTile<bf16>::BK : KTile<float>::BK;
+  const int M = g.K, N = g.R * g.S * g.C;
+  const long K = (long)g.N * g.P * g.Q;
   p.bm = M <= 64 ? 64 : 128;
   p.bn = N <= 64 ? 64 : 128;
-  if (dtype == BF16 && stem_direct_geom(geom(d)) && d->R == 7) {
+  if (esize == 2 && stem_direct_geom(g) && g.R == 7) {
     // the pixel-pair stem: K splits of whole 2-row pixel tiles (~256 splits), the layout the
     // direct kernel needs; the implicit-GEMM kernel takes the same splits (same sums)
-    const long tile_px = (long)STEM_PB * d->Q, ptiles = K / tile_px;
+    const long tile_px = (long)STEM_PB * g.Q, ptiles = K / tile_px;
     const long tps = (ptiles + 255) / 256;
     p.kper = (int)(tps * tile_px);
     p.splits = (int)((ptiles + tps - 1) / tps);
@@ -832,42 +898,76 @@ __global__ __launch_bounds__(512, 1) void stem_direct_wgrad_kernel(
 // (DmaRq: one pixel state per lane; MMDX_WGRAD_RQ=0 restores DmaR for A/B runs)
 static bool wgrad_rq_on() { return knobs().wgrad_rq; }
 
-template <typename T, class SB>
-static int wgrad_dma(const WgradPlan& p, const DenseR<T>& sa, const SB& sb, const EpiPartial& epi,
-                     int M, int N, int K, hipStream_t st) {
-  if constexpr (std::is_same<SB, Im2colR<T>>::value) {
-    if (wgrad_rq_on()) {
-      if (p.bm == 128 && p.bn == 128)
-        return launch_dma_ops<128, 128, DmaR<128, DenseR<T>>, DmaRq<128, SB>>(
-            sa, sb, epi, M, N, K, p.splits, p.kper, st);
-      if (p.bm == 128)
-        return launch_dma_ops<128, 64, DmaR<128, DenseR<T>>, DmaRq<64, SB>>(
-            sa, sb, epi, M, N, K, p.splits, p.kper, st);
-      if (p.bn == 128)
-        return launch_dma_ops<64, 128, DmaR<64, DenseR<T>>, DmaRq<128, SB>>(
-            sa, sb, epi, M, N, K, p.splits, p.kper, st);
-      return launch_dma_ops<64, 64, DmaR<64, DenseR<T>>, DmaRq<64, SB>>(sa, sb, epi, M, N, K,
-                                                                       p.splits, p.kper, st);
-    }
+// The weight gradient's kernel, as conv_fwd_path: the split-K plan, the B operand's loader (A,
+// dY, is DmaR or RLoad with it), the stages of the LDS-DMA kernel and the reduction.
+enum WgradB {  // DmaRq<Im2colR> (the 3x3 / strided im2col^T) | DmaR<Im2colR> (MMDX_WGRAD_RQ=0)
+               // | DmaR<PointWgradR> (a pointwise conv's im2col^T is x^T itself: dense, R-major,
+               // no window decode or tap tests) | igemm_kernel | stem_direct_wgrad_kernel
+  WB_DMARQ = 0, WB_DMAR, WB_DMAR_POINT, WB_RLOAD, WB_STEM_DIRECT };
+struct WgradPath {
+  WgradPlan plan;
+  int b, ns;  // WgradB; operand stages (0: not an LDS-DMA kernel)
+  bool reduce_z;
+};
+
+static WgradPath conv_wgrad_path(int esize, const ConvGeom& g) {
+  WgradPath w{plan_wgrad(esize, g), WB_RLOAD, 0, false};
+  const WgradPlan& p = w.plan;
+  const int M = g.K, N = g.R * g.S * g.C;
+  const long K = (long)g.N * g.P * g.Q;
+  w.reduce_z = wgrad_reduce_z(p.splits, (long)M * N);
+  if (esize != 2) return w;
+  // the pixel-pair stem: whole 2-row pixel tiles per split -> the direct kernel
+  const int tile_px = STEM_PB * g.Q;
+  if (stem_direct_geom(g) && stem_direct_on() && g.R == 7 && p.kper % tile_px == 0 &&
+      K % tile_px == 0 && tile_px <= 256 && g.W * (2 * (STEM_PB - 1) + g.R) <= 3 * 512) {
+    w.b = WB_STEM_DIRECT;
+  } else if (dma_geom_ok(g, false, 1 << 30) && K < (1 << 23)) {
+    // both operands R-major (M = Kout and N = R*S*C are multiples of 8)
+    w.b = is_pointwise(g) ? WB_DMAR_POINT : wgrad_rq_on() ? WB_DMARQ : WB_DMAR;
+    const long nwg = (long)((M + p.bm - 1) / p.bm) * ((N + p.bn - 1) / p.bn);
+    w.ns = use_three_stages(nwg * p.splits, (p.kper + 63) / 64) ? 3 : 2;
   }
-  if (p.bm == 128 && p.bn == 128)
-    return launch_dma_ops<128, 128, DmaR<128, DenseR<T>>, DmaR<128, SB>>(sa, sb, epi, M, N, K,
-                                                                        p.splits, p.kper, st);
-  if (p.bm == 128)
-    return launch_dma_ops<128, 64, DmaR<128, DenseR<T>>, DmaR<64, SB>>(sa, sb, epi, M, N, K,
-                                                                      p.splits, p.kper, st);
-  if (p.bn == 128)
-    return launch_dma_ops<64, 128, DmaR<64, DenseR<T>>, DmaR<128, SB>>(sa, sb, epi, M, N, K,
-                                                                      p.splits, p.kper, st);
-  return launch_dma_ops<64, 64, DmaR<64, DenseR<T>>, DmaR<64, SB>>(sa, sb, epi, M, N, K,
-                                                                  p.splits, p.kper, st);
+  return w;
+}
+
+// f(BM, BN) as integral constants for the plan's block tile
+template <class F>
+static int wgrad_tile(const WgradPlan& p, F&& f) {
+  using C64 = std::integral_constant<int, 64>;
+  using C128 = std::integral_constant<int, 128>;
+  if (p.bm == 128 && p.bn == 128) return f(C128{}, C128{});
+  if (p.bm == 128) return f(C128{}, C64{});
+  if (p.bn == 128) return f(C64{}, C128{});
+  return f(C64{}, C64{});
+}
+
+// OB: DmaRq exists for Im2colR only (PointWgradR only ever meets DmaR)
+template <typename T, class SB>
+static int wgrad_dma(const WgradPath& w, const DenseR<T>& sa, const SB& sb, const EpiPartial& epi,
+                     int M, int N, int K, hipStream_t st) {
+  const WgradPlan& p = w.plan;
+  if constexpr (std::is_same<SB, Im2colR<T>>::value) {
+    if (w.b == WB_DMARQ)
+      return wgrad_tile(p, [&](auto bm, auto bn) {
+        constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+        return launch_dma_ops<BM, BN, DmaR<BM, DenseR<T>>, DmaRq<BN, SB>>(
+            w.ns, sa, sb, epi, M, N, K, p.splits, p.kper, st);
+      });
+  }
+  return wgrad_tile(p, [&](auto bm, auto bn) {
+    constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+    return launch_dma_ops<BM, BN, DmaR<BM, DenseR<T>>, DmaR<BN, SB>>(
+        w.ns, sa, sb, epi, M, N, K, p.splits, p.kper, st);
+  });
 }
 
 template <typename T>
 static int conv_wgrad_t(const mmdx_conv_desc* d, int cm, const void* x, const void* dy,
                         float* dw, float beta, void* ws, size_t ws_bytes, hipStream_t st) {
   const ConvGeom g = geom(d);
-  const WgradPlan p = plan_wgrad(sizeof(T) == 2 ? BF16 : F32, d);
+  const WgradPath w = conv_wgrad_path((int)sizeof(T), g);
+  const WgradPlan& p = w.plan;
   const int M = g.K, N = g.R * g.S * g.C;
   const long Kl = (long)g.N * g.P * g.Q;
   MMDX_CHECK_ARG(Kl < (1L << 31), "conv wgrad: N*P*Q too large");
@@ -878,51 +978,29 @@ static int conv_wgrad_t(const mmdx_conv_desc* d, int cm, const void* x, const vo
   DenseR<T> sa{(const T*)dy, g.K, M, true, K};
   const Im2colR<T> sb = make_im2colr<T>((const T*)x, g, N);  // one 64-pixel K tile per issue
   EpiPartial epi{(float*)ws, M, N};
-  int rc;
+  int rc = -1;
   if constexpr (sizeof(T) == 2) {
-    // the pixel-pair stem: whole 2-row pixel tiles per split -> the direct kernel
-    const int tile_px = STEM_PB * g.Q;
-    if (stem_direct_geom(g) && stem_direct_on() && g.R == 7 && p.kper % tile_px == 0 &&
-        K % tile_px == 0 && tile_px <= 256 && g.W * (2 * (STEM_PB - 1) + g.R) <= 3 * 512) {
+    if (w.b == WB_STEM_DIRECT) {
+      const int tile_px = STEM_PB * g.Q;
       const size_t lds = (size_t)tile_px * STEM_LDD * 2 +
                          (size_t)(2 * (STEM_PB - 1) + g.R) * g.W * 16;
       hipLaunchKernelGGL(stem_direct_wgrad_kernel<7>, dim3(p.splits), dim3(512), lds, st,
                          (const bf16*)x, (const bf16*)dy, (float*)ws, g.H, g.W, g.P, g.Q,
                          p.kper / tile_px, K / tile_px);
       MMDX_LAUNCH_CHECK();
-      wgrad_reduce((const float*)ws, p.splits, g.K, g.C, cm, g.R * g.S, dw, beta, st);
-      MMDX_LAUNCH_CHECK();
-      return 0;
+      rc = 0;
+    } else if (w.b == WB_DMAR_POINT) {
+      rc = wgrad_dma<T>(w, sa, PointWgradR<T>{{(const T*)x, g.C, N, true, K}}, epi, M, N, K, st);
+    } else if (w.b != WB_RLOAD) {
+      rc = wgrad_dma<T>(w, sa, sb, epi, M, N, K, st);
     }
   }
-  if constexpr (sizeof(T) == 2) {
-   if (dma_geom_ok(g, false, 1 << 30) && K < (1 << 23)) {
-    // LDS-DMA wgrad: both operands R-major (M = Kout and N = R*S*C are multiples of 8).  A
-    // 1x1 / stride-1 / unpadded conv's im2col^T is x^T itself: a dense R-major operand
-    // (no window decode or tap tests)
-    if (is_pointwise(g))
-      rc = wgrad_dma<T>(p, sa, PointWgradR<T>{{(const T*)x, g.C, N, true, K}}, epi, M, N, K,
-                        st);
-    else
-      rc = wgrad_dma<T>(p, sa, sb, epi, M, N, K, st);
-    if (rc) return rc;
-    wgrad_reduce((const float*)ws, p.splits, g.K, g.C, cm, g.R * g.S, dw, beta, st);
-    MMDX_LAUNCH_CHECK();
-    return 0;
-   }
-  }
-  typedef RLoad<T, 128, DenseR<T>> A128;
-  typedef RLoad<T, 64, DenseR<T>> A64;
-  typedef RLoad<T, 128, Im2colR<T>> B128;
-  typedef RLoad<T, 64, Im2colR<T>> B64;
-  if (p.bm == 128 && p.bn == 128)
-    rc = launch<T, 128, 128, A128, B128>(sa, sb, epi, M, N, K, p.splits, p.kper, st);
-  else if (p.bm == 128)
-    rc = launch<T, 128, 64, A128, B64>(sa, sb, epi, M, N, K, p.splits, p.kper, st);
-  else if (p.bn == 128)
-    rc = launch<T, 64, 128, A64, B128>(sa, sb, epi, M, N, K, p.splits, p.kper, st);
-  else
-    rc = launch<T, 64, 64, A64, B64>(sa, sb, epi, M, N, K, p.splits, p.kper, st);
+  if (w.b == WB_RLOAD)
+    rc = wgrad_tile(p, [&](auto bm, auto bn) {
+      constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+      return launch<T, BM, BN, RLoad<T, BM, DenseR<T>>, RLoad<T, BN, Im2colR<T>>>(
+          sa, sb, epi, M, N, K, p.splits, p.kper, st);
+    });
   if (rc) return rc;
   wgrad_reduce((const float*)ws, p.splits, g.K, g.C, cm, g.R * g.S, dw, beta, st);
   MMDX_LAUNCH_CHECK();
@@ -1043,7 +1121,7 @@ extern "C" int mmdx_conv_dgrad_accmask(int dtype, const mmdx_conv_desc* d, const
 }
 
 extern "C" size_t mmdx_conv_wgrad_workspace_size(int dtype, const mmdx_conv_desc* d) {
-  const WgradPlan p = plan_wgrad(dtype, d);
+  const WgradPlan p = plan_wgrad(dtype == BF16 ? 2 : 4, geom(d));
   return (size_t)p.splits * d->K * d->R * d->S * d->C * sizeof(float);
 }
 
@@ -1065,23 +1143,54 @@ extern "C" int mmdx_conv_wgrad(int dtype, const mmdx_conv_desc* d, int c_master,
 extern "C" int mmdx_conv_dgrad_stat_blocks(int dtype, const mmdx_conv_desc* d) {
   if (dtype != BF16 || !d || d->K % 64 != 0 || d->C % 8 != 0) return 0;
   const ConvGeom g = geom(d);
-  if (g.sh == 1 && g.sw == 1) {
-    if (!dma_geom_ok(g, true, 32, (long)g.N * g.H * g.W)) return 0;
-    return (int)(((long)g.N * g.H * g.W + 127) / 128);
-  }
-  // every phase has at most N*H*W rows: this check passing implies each phase's launch passes
-  if (!dma_geom_ok(g, false, 32, (long)g.N * g.H * g.W)) return 0;
+  const ConvPath p = conv_dgrad_path(2, g, 0.f);
+  if (p.loader == LOAD_KLOAD) return 0;
+  if (p.family != FAM_PHASES_MERGED) return (int)(((long)g.N * g.H * g.W + 127) / 128);
   long tiles = 0;
-  for (int a = 0; a < g.sh; ++a)
-    for (int b = 0; b < g.sw; ++b) {
-      const int Hp = g.H > a ? (g.H - a + g.sh - 1) / g.sh : 0;
-      const int Wp = g.W > b ? (g.W - b + g.sw - 1) / g.sw : 0;
-      const int r0 = (a + g.ph) % g.sh, s0 = (b + g.pw) % g.sw;
-      if (Hp == 0 || Wp == 0) continue;
-      if (r0 >= g.R || s0 >= g.S) return 0;  // an unreached phase: no fused statistics
-      tiles += ((long)g.N * Hp * Wp + 127) / 128;
-    }
-  return (int)tiles;
+  bool unreached = false;  // a phase no tap reaches: no fused statistics
+  for_each_phase(g, 0.f, [&](int, int, const PhaseGeom&, int M, int K) {
+    unreached |= K == 0;
+    tiles += (M + 127) / 128;
+  });
+  return unreached ? 0 : (int)tiles;
+}
+
+// Host only: the path the pass's launch takes, from the functions the launch itself calls.
+extern "C" int mmdx_conv_describe(int dtype, int pass, const mmdx_conv_desc* d, float beta,
+                                  char* out, size_t n) {
+  MMDX_CHECK_ARG(out && n > 0, "mmdx_conv_describe: no output buffer");
+  out[0] = 0;
+  MMDX_CHECK_ARG(dtype == F32 || dtype == BF16, "mmdx_conv_describe: bad dtype %d", dtype);
+  MMDX_CHECK_ARG(pass >= 0 && pass <= 2, "mmdx_conv_describe: bad pass %d", pass);
+  int rc = check_desc(d, dtype == BF16 ? 8 : 4);
+  if (rc) return rc;
+  static const char* const fam[] = {"point", "fast", "generic", "phases-merged", "phases-each"};
+  static const char* const load[] = {"kload", "dma", "dma-lanetap"};
+  static const char* const tile[] = {"128x64", "128x128", "128x128-8w", "256x64"};
+  static const char* const wb[] = {"DmaRq", "DmaR", "DmaR-point", "RLoad"};
+  const int esize = dtype == BF16 ? 2 : 4;
+  const ConvGeom g = geom(d);
+  int w;
+  if (pass == 2) {
+    const WgradPath p = conv_wgrad_path(esize, g);
+    char op[32], ns[8] = "";
+    if (p.ns) snprintf(ns, sizeof ns, "/ns%d", p.ns);
+    if (p.b == WB_STEM_DIRECT) snprintf(op, sizeof op, "stem-direct");
+    else snprintf(op, sizeof op, "%dx%d/%s%s", p.plan.bm, p.plan.bn, wb[p.b], ns);
+    w = snprintf(out, n, "%s/%s/s%d/k%d", op, p.reduce_z ? "reduce-z" : "reduce", p.plan.splits,
+                 p.plan.kper);
+  } else {
+    const ConvPath p = pass == 0 ? conv_fwd_path(esize, g, stem_direct_on())
+                                 : conv_dgrad_path(esize, g, beta);
+    // the stage count is named where use_three_stages chose it (kmajor_tile)
+    const bool ruled = p.ns && p.family <= FAM_GENERIC && p.tile <= TILE_128x128;
+    char ns[8] = "";
+    if (ruled) snprintf(ns, sizeof ns, "/ns%d", p.ns);
+    if (p.family == FAM_STEM_DIRECT) w = snprintf(out, n, "stem-direct");
+    else w = snprintf(out, n, "%s/%s/%s%s", fam[p.family], load[p.loader], tile[p.tile], ns);
+  }
+  MMDX_CHECK_ARG(w >= 0 && (size_t)w < n, "mmdx_conv_describe: buffer of %zu bytes too small", n);
+  return 0;
 }
 
 extern "C" int mmdx_conv_dgrad_bnstat(int dtype, const mmdx_conv_desc* d, const void* dy,

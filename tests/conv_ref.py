@@ -2,8 +2,10 @@
 only): forward, data gradient and weight gradient of a full descriptor, their sums of |terms|,
 the NHWC / packed layouts the kernels read and write, the two operand families of
 tests/test_conv_reference_gpu.py (integer and Gaussian) with their comparisons, the forward
-epilogue's BatchNorm slabs, and expected_path(): a host mirror of the dispatcher's predicates
-that names the kernel path each case takes.
+epilogue's BatchNorm slabs, and expected_path(): a host mirror of conv.hip's path functions
+(conv_fwd_path, conv_dgrad_path, conv_wgrad_path) that names the kernel path each case takes.
+tests/test_conv_ref_cpu.py holds it against mmdx_conv_describe, which prints what the launches
+themselves consult, for the case table, the threshold shapes and the ResNet trunks.
 
 A descriptor is the tuple cfg = (N, C, H, W, K, R, S, sh, sw, ph, pw): C is the channel count the
 kernels see (a multiple of the vector width); c_master <= C is the master weight's / image's."""
@@ -291,7 +293,7 @@ BK = {BF16: 64, F32: 32}          # igemm.h KTile<T>::BK
 NARROW_BELOW = 384                # conv.hip kNarrowBelow
 WGRAD_TARGET = 256                # common.h: MMDX_WGRAD_TARGET's default
 _KNOBS = {"MMDX_CONV_N64_WIDE": -1, "MMDX_CONV_8W128": 1, "MMDX_WGRAD_RQ": 1,
-          "MMDX_WGRAD_TARGET": WGRAD_TARGET}
+          "MMDX_WGRAD_TARGET": WGRAD_TARGET, "MMDX_STEM_DIRECT": 1}
 
 
 def _cdiv(a, b):
@@ -328,7 +330,7 @@ def _stages(blocks, ktiles):
 
 
 def _gemm_path(operand, M, N, K, dma, kn, lane_tap=False):
-    """conv.hip conv_gemm_epi: loader and tile of a k-major conv GEMM [M, N, K]."""
+    """conv.hip kmajor_tile: loader, tile and stages of a k-major conv GEMM [M, N, K]."""
     if not dma:
         return f"{operand}/kload/{'128x64' if N <= 64 else '128x128'}"
     dname = "dma-lanetap" if lane_tap else "dma"
@@ -363,12 +365,17 @@ def phases(cfg):
 
 
 def plan_wgrad(cfg, dt, target=WGRAD_TARGET):
-    """conv.hip plan_wgrad (outside the pixel-pair stem): tile, split count, pixels per split."""
+    """conv.hip plan_wgrad: tile, split count, pixels per split (the pixel-pair stem: about 256
+    splits of whole 2-row pixel tiles)."""
     N, C, H, W, K, R, S = cfg[:7]
     P, Q = out_size(cfg)
     M, Nn, Kl = K, R * S * C, N * P * Q
     bm = 64 if M <= 64 else 128
     bn = 64 if Nn <= 64 else 128
+    if dt == BF16 and _stem_direct_geom(cfg) and R == 7:
+        ptiles = Kl // (2 * Q)
+        tps = _cdiv(ptiles, 256)
+        return SimpleNamespace(bm=bm, bn=bn, splits=_cdiv(ptiles, tps), kper=tps * 2 * Q)
     tiles = _cdiv(M, bm) * _cdiv(Nn, bn)
     ktiles = _cdiv(Kl, BK[dt])
     s = max(1, min(_cdiv(target, tiles), ktiles // 16))
@@ -384,21 +391,23 @@ def dgrad_stat_blocks(cfg, dt):
         return 0
     if sh == 1 and sw == 1:
         return _cdiv(N * H * W, 128) if dma_geom_ok(cfg, True, 32, N * H * W) else 0
-    if not dma_geom_ok(cfg, False, 32, N * H * W):
+    if not dma_geom_ok(cfg, False, 32, N * _cdiv(H, sh) * _cdiv(W, sw)):   # not phases-merged
         return 0
     ph_ = phases(cfg)
     return 0 if any(p["K"] == 0 for p in ph_) else sum(_cdiv(p["M"], 128) for p in ph_)
 
 
-def expected_path(cfg, dt, knobs=None):
+def expected_path(cfg, dt, knobs=None, beta=0.0):
     """The kernel path conv.hip's dispatcher takes for this descriptor: names for fwd (also
-    mmdx_conv_fwd_bn_eval's), dgrad (at beta 0) and wgrad, and the weight-gradient plan.
+    mmdx_conv_fwd_bn_eval's, but for the direct stem), dgrad (at this beta) and wgrad, and the
+    weight-gradient plan; desc(pass) is mmdx_conv_describe's string.
 
     fwd / stride-1 dgrad: <operand>/<loader>/<tile>[/ns<stages>], operand point | fast | generic
     (PointFwdK / PointDgradK, Im2colK / DgradK <true>, <false>), loader dma | dma-lanetap (the
     power-of-two self-decoding gather) | kload.  Strided dgrad with K % BK == 0:
     phases-merged/dma/<tile> or phases-each/kload/<tile>.  wgrad: <bm>x<bn>/<operand>/ns<stages>/
-    <reduction>, operand DmaRq | DmaR | DmaR-point | RLoad, reduction reduce | reduce-z."""
+    <reduction>, operand DmaRq | DmaR | DmaR-point | RLoad, reduction reduce | reduce-z.  The
+    pixel-pair stem's direct kernels (MMDX_STEM_DIRECT): stem-direct, stem-direct/<reduction>."""
     kn = dict(_KNOBS)
     kn.update(knobs or {})
     N, C, H, W, K, R, S, sh, sw, ph, pw = cfg
@@ -406,9 +415,9 @@ def expected_path(cfg, dt, knobs=None):
     bk, bf = BK[dt], dt == BF16
     out = SimpleNamespace()
 
-    # conv_fwd_t
+    # conv_fwd_path
     M, Kg = N * P * Q, R * S * C
-    if bf and _stem_direct_geom(cfg):
+    if bf and kn["MMDX_STEM_DIRECT"] and _stem_direct_geom(cfg):
         out.fwd = "stem-direct"
     elif C % bk == 0 and is_pointwise(cfg):
         out.fwd = _gemm_path("point", M, K, Kg, bf and dma_geom_ok(cfg, False, 32, M), kn)
@@ -419,11 +428,12 @@ def expected_path(cfg, dt, knobs=None):
         out.fwd = _gemm_path("generic", M, K, Kg, bf and pow2 and dma_geom_ok(cfg, False, 64, M),
                              kn, lane_tap=True)
 
-    # conv_dgrad_t
+    # conv_dgrad_path: a phase no tap reaches is launched (to write zeros) at beta 0 only
     out.phases = phases(cfg) if (sh > 1 or sw > 1) else []
     if (sh > 1 or sw > 1) and K % bk == 0:
         rows = N * _cdiv(H, sh) * _cdiv(W, sw)
-        tiles128 = sum(_cdiv(p["M"], 128) * _cdiv(C, 128) for p in out.phases)
+        tiles128 = sum(_cdiv(p["M"], 128) * _cdiv(C, 128) for p in out.phases
+                       if p["K"] or beta == 0)
         if bf and dma_geom_ok(cfg, False, 32, rows):
             tile = "128x64" if C <= 64 or tiles128 < NARROW_BELOW else "128x128"
             out.dgrad = f"phases-merged/dma/{tile}"
@@ -438,16 +448,35 @@ def expected_path(cfg, dt, knobs=None):
         else:
             out.dgrad = _gemm_path("generic", M, C, Kg, False, kn)
 
-    # conv_wgrad_t
+    # conv_wgrad_path
     p = plan_wgrad(cfg, dt, kn["MMDX_WGRAD_TARGET"])
     out.plan = p
     Kl, total = N * P * Q, K * R * S * C
+    red = "reduce" if total % 4 or p.splits < 128 else "reduce-z"
+    out.desc = lambda pas: (out.fwd, out.dgrad, f"{out.wgrad}/s{p.splits}/k{p.kper}")[pas]
+    if (bf and _stem_direct_geom(cfg) and kn["MMDX_STEM_DIRECT"] and R == 7
+            and p.kper % (2 * Q) == 0 and Kl % (2 * Q) == 0 and 2 * Q <= 256
+            and W * (2 + R) <= 3 * 512):
+        out.wgrad = f"stem-direct/{red}"
+        return out
     if bf and dma_geom_ok(cfg, False, 1 << 30) and Kl < 1 << 23:
         op = "DmaR-point" if is_pointwise(cfg) else "DmaRq" if kn["MMDX_WGRAD_RQ"] else "DmaR"
         blocks = _cdiv(K, p.bm) * _cdiv(R * S * C, p.bn) * p.splits
         op += f"/ns{_stages(blocks, _cdiv(p.kper, 64))}"
     else:
         op = "RLoad"
-    red = "reduce" if total % 4 or p.splits < 128 else "reduce-z"
     out.wgrad = f"{p.bm}x{p.bn}/{op}/{red}"
     return out
+
+
+def describe(lib, cfg, dt, pas, beta=0.0):
+    """mmdx_conv_describe for this descriptor (under the knobs the library currently holds);
+    pas 0 fwd, 1 dgrad, 2 wgrad."""
+    import ctypes
+    from mmdx import _lib as L
+    N, C, H, W, K, R, S, sh, sw, ph, pw = cfg
+    d = L.ConvDesc(N, H, W, C, K, R, S, sh, sw, ph, pw, *out_size(cfg))
+    buf = ctypes.create_string_buffer(96)
+    rc = lib.mmdx_conv_describe(L.dtype_code(dt), pas, d, beta, buf, len(buf))
+    assert rc == 0, lib.mmdx_last_error().decode()
+    return buf.value.decode()

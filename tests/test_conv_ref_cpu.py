@@ -131,6 +131,7 @@ FWD_PATHS = {
     "fast/dma/128x128-8w", "fast/dma/256x64", "generic/dma-lanetap/128x64/ns2",
     "generic/dma-lanetap/128x64/ns3", "generic/kload/128x64", "generic/kload/128x128",
     "point/kload/128x64", "fast/kload/128x64", "fast/kload/128x128",   # fp32
+    "stem-direct",                                                     # the pixel-pair stem
 }
 DGRAD_PATHS = {
     "point/dma/128x64/ns2", "point/dma/128x128-8w", "fast/dma/128x64/ns3", "fast/dma/256x64",
@@ -144,8 +145,14 @@ WGRAD_PATHS = {
     "64x128/DmaRq/ns3/reduce", "128x64/DmaRq/ns2/reduce", "128x128/DmaRq/ns2/reduce",
     "128x128/DmaRq/ns3/reduce", "128x128/DmaR/ns3/reduce",
     "64x64/RLoad/reduce", "64x128/RLoad/reduce", "128x128/RLoad/reduce",   # fp32
+    "stem-direct/reduce",                                                  # the pixel-pair stem
 }
 RUNS = [(cid, None) for cid in ALL] + R.KNOB_RUNS
+# The pixel-pair stem (mmdx_stem_pair_desc of a 2 x 3 x 224 x 224 batch, 7x7 / 2 / pad 3): its
+# direct kernels by default, the implicit GEMM with MMDX_STEM_DIRECT=0.  Mirror only: on the GPU
+# tests/test_stem_pair_gpu.py and the trunk tests run it.
+STEM_PAIR = (2, 8, 230, 115, 64, 7, 4, 2, 1, 0, 0)
+STEM_RUNS = [(STEM_PAIR, None), (STEM_PAIR, {"MMDX_STEM_DIRECT": 0})]
 
 
 def _reached():
@@ -157,6 +164,11 @@ def _reached():
         if cid not in R.WGRAD_ONLY:
             fwd.add(p.fwd)
             dgrad.add(p.dgrad)
+    for cfg, kn in STEM_RUNS:               # the stem has no data gradient
+        p = R.expected_path(cfg, BF16, kn)
+        fwd.add(p.fwd)
+        wgrad.add(p.wgrad)
+    dgrad.add(R.expected_path(R.case(5)[0], BF16, None, beta=1.0).dgrad)
     return fwd, dgrad, wgrad
 
 
@@ -265,6 +277,108 @@ def test_plan_mirror_matches_the_library():
         assert L.lib().mmdx_conv_dgrad_stat_blocks(L.dtype_code(dt), d) == R.dgrad_stat_blocks(cfg, dt)
         assert L.lib().mmdx_conv_fwd_stat_rows(d) == 128
         assert L.lib().mmdx_conv_fwd_stat_blocks(d) == (N * P * Q + 127) // 128
+
+
+# ------------------------------------------------------- the mirror against mmdx_conv_describe
+K1 = (1, 64, 1, 191 * 128, 256, 1, 1, 1, 1, 0, 0)       # test_mirror_predicates' thresholds
+K2 = (1, 64, 1, 192 * 128, 256, 1, 1, 1, 1, 0, 0)
+N1 = (1, 64, 1, 1023 * 256, 64, 1, 1, 1, 1, 0, 0)
+N2 = (1, 64, 1, 1023 * 256 + 1, 64, 1, 1, 1, 1, 0, 0)
+# 1x1 / stride 2 over four phases of 104 tiles of 128 x 128 each, one of them reached: 416 tiles
+# at beta 0 (all launched), 104 at beta 1, on the two sides of kNarrowBelow
+B1 = (13, 128, 64, 64, 64, 1, 1, 2, 2, 0, 0)
+KNOB_NAMES = ["MMDX_CONV_N64_WIDE", "MMDX_CONV_8W128", "MMDX_WGRAD_RQ", "MMDX_STEM_DIRECT"]
+
+
+def _resnet_convs():
+    """Every distinct conv of ResNet-18 and ResNet-50 at 224 x 224 (enumerated from the modules
+    by tools/conv_bench.py) at three batches, as descriptors with the channels the kernels see;
+    the stems both channel-padded and as the pixel-pair conv of mmdx_stem_pair_desc."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                    "tools"))
+    import conv_bench
+    from mmdx import _lib as L
+    cfgs, pairs = set(), set()
+    for arch in ("resnet18", "resnet50"):
+        for (H, W, C, K, k, s, p), info in conv_bench.shapes(arch, 224).items():
+            for B in (64, 128, 256):
+                cfgs.add((B, R.pad_channels(C, BF16), H, W, K, k, k, s, s, p, p))
+                if info["tag"] == "stem":
+                    d = L.ConvDesc()
+                    L.call("mmdx_stem_pair_desc", B, C, H, W, K, k, k, s, p, d)
+                    pairs.add((d.N, d.C, d.H, d.W, d.K, d.R, d.S, d.stride_h, d.stride_w,
+                               d.pad_h, d.pad_w))
+    return sorted(cfgs), sorted(pairs)
+
+
+def _assert_mirror_is_describe(lib, cfg, dt, kn, what, beta=0.0):
+    e = R.expected_path(cfg, dt, kn, beta)
+    for pas in ((1,) if beta else (0, 1, 2)):
+        assert e.desc(pas) == R.describe(lib, cfg, dt, pas, beta), (what, pas, kn, beta)
+    return e
+
+
+def test_mirror_equals_describe(knobs):
+    """expected_path() == mmdx_conv_describe() (which prints what the launches consult) for fwd,
+    dgrad at beta 0 and wgrad: the case table and its knob runs, the threshold shapes, the
+    ResNet-18 / -50 trunks at batch 64 / 128 / 256, the pixel-pair stem with and without its
+    direct kernels, and the strided dgrad at beta 1, where unreached phases leave the grid."""
+    from mmdx import _lib as L
+    lib = L.lib()
+
+    def set_knobs(kn):
+        for name in KNOB_NAMES:
+            knobs(name, (kn or {}).get(name))
+
+    for cid, kn in RUNS:
+        cfg, cm, dt = R.case(cid)
+        set_knobs(kn)
+        _assert_mirror_is_describe(lib, cfg, dt, kn, cid)
+    for cfg, kn in [(K1, None), (K2, None), (N1, None), (N2, None), (B1, None),
+                    (K2, {"MMDX_CONV_8W128": 0}), (N2, {"MMDX_CONV_N64_WIDE": 0})] + STEM_RUNS:
+        set_knobs(kn)
+        _assert_mirror_is_describe(lib, cfg, BF16, kn, cfg)
+    d = L.ConvDesc()
+    L.call("mmdx_stem_pair_desc", 2, 3, 224, 224, 64, 7, 7, 2, 3, d)
+    assert STEM_PAIR == (d.N, d.C, d.H, d.W, d.K, d.R, d.S, d.stride_h, d.stride_w, d.pad_h,
+                         d.pad_w)
+    cfgs, pairs = _resnet_convs()
+    assert len(cfgs) == 3 * 29 and len(pairs) == 3     # 29 distinct convs over the two trunks
+    for direct in (1, 0):
+        kn = {"MMDX_STEM_DIRECT": direct}
+        set_knobs(kn)
+        for cfg in cfgs + pairs:
+            _assert_mirror_is_describe(lib, cfg, BF16, kn, cfg)
+    # dgrad at beta 1: case 5 launches one phase of its four; B1 changes tile with it
+    set_knobs(None)
+    for cfg in (R.case(5)[0], B1):
+        _assert_mirror_is_describe(lib, cfg, BF16, None, cfg, beta=1.0)
+    assert R.expected_path(B1, BF16).dgrad == "phases-merged/dma/128x128"
+    assert R.expected_path(B1, BF16, None, 1.0).dgrad == "phases-merged/dma/128x64"
+    e = R.expected_path(pairs[0], BF16)
+    assert (e.fwd, e.wgrad) == ("stem-direct", "stem-direct/reduce-z") and e.plan.splits == 256
+
+
+def test_describe_rejects_bad_arguments():
+    import ctypes
+    from mmdx import _lib as L
+    lib = L.lib()
+    cfg = R.case(1)[0]
+    N, C, H, W, K, Rr, S, sh, sw, ph, pw = cfg
+    d = L.ConvDesc(N, H, W, C, K, Rr, S, sh, sw, ph, pw, *R.out_size(cfg))
+    buf = ctypes.create_string_buffer(96)
+    assert lib.mmdx_conv_describe(L.BF16, 0, d, 0.0, buf, 96) == 0
+    assert buf.value.decode() == R.expected_path(cfg, BF16).fwd
+    assert lib.mmdx_conv_describe(L.BF16, 0, d, 0.0, buf, 4) != 0          # short buffer
+    assert lib.mmdx_conv_describe(L.BF16, 0, d, 0.0, None, 96) != 0
+    assert lib.mmdx_conv_describe(7, 0, d, 0.0, buf, 96) != 0 and buf.value == b""
+    assert lib.mmdx_conv_describe(L.F16, 0, d, 0.0, buf, 96) != 0          # fp16: no conv path
+    assert lib.mmdx_conv_describe(L.BF16, 3, d, 0.0, buf, 96) != 0
+    assert lib.mmdx_conv_describe(L.BF16, -1, d, 0.0, buf, 96) != 0
+    assert lib.mmdx_conv_describe(L.BF16, 0, None, 0.0, buf, 96) != 0
+    d.P += 1                                                                # inconsistent
+    assert lib.mmdx_conv_describe(L.BF16, 0, d, 0.0, buf, 96) != 0
 
 
 # ------------------------------------------------------------------------------ sensitivity
