@@ -1063,6 +1063,31 @@ int mmdx_clahe_apply(const uint8_t* pixels, size_t pixel_bytes,
                      const uint8_t* luts, size_t lut_bytes, uint8_t* out, size_t out_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------- similar-case retrieval
+ * Exact top-k inner-product search (mmdx/retrieval.py: reference_search is the definition).
+ * index [N][d] row-major, queries [nq][d], both `dtype` (fp32, bf16 or fp16), 16-byte aligned.
+ * score[i][j] = sum_t q[i][t] x[j][t], accumulated in fp32 by one MFMA chain over d in a fixed
+ * order: the bits of a score depend on the query row and the index row alone, not on N, nq, k,
+ * the row's position or the grid.  A NaN score counts as -inf; a zero score is +0.0.  Row
+ * exclude[i] (int32 [nq] on the device, -1 = none, NULL = none for all; entries outside [-1, N)
+ * match no row: the caller checks the range) is removed for query i.  out_ids int32 [nq][k] and
+ * out_scores fp32 [nq][k]: the first k remaining rows under (score descending, id ascending);
+ * slots past the number of remaining rows hold id -1 and score -inf.
+ *
+ * Two launches on `stream` (select: one streaming pass over the index per group of 16 queries,
+ * each block's k best per query into the workspace; merge: one block per query), no [nq][N]
+ * score matrix, no atomics in global memory, no counter: bit-reproducible, and a search over
+ * slices of the index merged under the same order equals the search over the whole.
+ * Limits (rejected before any launch): 1 <= N <= 2^24, d % 32 == 0, 32 <= d <= 4096,
+ * 1 <= nq <= 64, 1 <= k <= 64.  workspace: mmdx_topk_similar_workspace_size bytes (blocks * nq *
+ * k pairs; 0 for an unsupported shape), 16-byte aligned; outputs overlap neither each other nor
+ * an input.  mmdx_topk_rows_per_block: the index rows of one block step (a tile edge for tests). */
+int mmdx_topk_rows_per_block(void);
+size_t mmdx_topk_similar_workspace_size(long N, int d, int nq, int k);
+int mmdx_topk_similar(void* stream, int dtype, const void* queries, const void* index, long N,
+                      int d, int nq, int k, const int* exclude, float* out_scores, int* out_ids,
+                      void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,5 +10,6 @@ from .training_pipeline import image_transfom_into_tensor, tokenize_patient_deta
 from .training_pipeline import parse_s3_url, get_image_from_s3  # noqa: F401
 
 from mmdx.inference_pipeline import (  # noqa: F401
-    inference, inference_explained, inference_tests, latest_version, load_model_bundle,
+    inference, inference_explained, inference_similar, inference_tests, latest_version,
+    load_model_bundle,
     load_model_from_hopsworks_model_registry, save_model_bundle)

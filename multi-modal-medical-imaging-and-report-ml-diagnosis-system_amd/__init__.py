@@ -16,5 +16,7 @@ from .augment import Augment  # noqa: F401
 from .clahe import Clahe  # noqa: F401
 from .losses import DiseaseLoss  # noqa: F401
 from . import bootstrap  # noqa: F401
+from . import retrieval  # noqa: F401
+from .retrieval import CaseIndex  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1100,3 +1100,82 @@ def clahe(images, clip_limit=2.0, tiles=(8, 8), return_luts=False, device=None):
         t = luts[lo:lo + c * ty * tx * 256].view(c, ty, tx, 256)
         tabs.append(t[0] if len(shp) == 2 else t)
     return (res, tabs) if return_luts else res
+
+
+# ----------------------------------------------------------------------------- retrieval
+TOPK_MAX_N, TOPK_MAX_D, TOPK_MAX_NQ, TOPK_MAX_K = 1 << 24, 4096, 64, 64
+
+
+def topk_rows_per_block() -> int:
+    """The index rows one block of the select kernel scores per step (a tile edge for tests)."""
+    return int(L.lib().mmdx_topk_rows_per_block())
+
+
+def topk_similar(queries, index, k, exclude=None, out=None):
+    """Exact top-k inner-product search (mmdx_topk_similar; mmdx.retrieval.reference_search is
+    the definition): queries [nq, d] against index [N, d], both fp32, bf16 or fp16 on one GPU,
+    contiguous; score = the fp32-accumulated dot product, NaN counting as -inf; row exclude[i]
+    (int32 [nq], -1 = none) is removed for query i.  Returns (scores fp32 [nq, k], ids int32
+    [nq, k]): the first k remaining rows under (score descending, id ascending), padded with
+    (-inf, -1); `out` = (scores, ids) reuses the caller's tensors.  Limits: 1 <= N <= 2^24,
+    d % 32 == 0, 32 <= d <= 4096, 1 <= nq <= 64, 1 <= k <= 64, exclude in [-1, N) (checked in one
+    device reduction, the only host sync here, and only with `exclude`).  A wrong dtype is a
+    TypeError; a wrong shape, device or layout or a limit exceeded a ValueError; nothing is
+    copied, cast or launched then."""
+    name = "topk_similar"
+    if not torch.is_tensor(queries) or not torch.is_tensor(index):
+        raise TypeError(f"{name} takes tensors")
+    dt = L.dtype_code(index.dtype)
+    if queries.dtype != index.dtype:
+        raise TypeError(f"{name}: queries are {queries.dtype}, the index {index.dtype}")
+    if exclude is not None and (not torch.is_tensor(exclude) or exclude.dtype != torch.int32):
+        raise TypeError(f"{name}: exclude must be an int32 tensor")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{name}: k must be an int, got {type(k).__name__}")
+    k = int(k)
+    if queries.dim() != 2 or index.dim() != 2 or queries.shape[1] != index.shape[1]:
+        raise ValueError(f"{name}: queries {tuple(queries.shape)} and index "
+                         f"{tuple(index.shape)} are not [nq, d] and [N, d]")
+    (nq, d), N = queries.shape, index.shape[0]
+    if not 1 <= N <= TOPK_MAX_N or d % 32 or not 32 <= d <= TOPK_MAX_D:
+        raise ValueError(f"{name}: N = {N}, d = {d} outside 1 <= N <= 2^24, d a multiple of 32 "
+                         f"in [32, {TOPK_MAX_D}]")
+    if not 1 <= nq <= TOPK_MAX_NQ or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"{name}: nq = {nq}, k = {k} outside [1, {TOPK_MAX_NQ}] and "
+                         f"[1, {TOPK_MAX_K}]")
+    if exclude is not None and tuple(exclude.shape) != (nq,):
+        raise ValueError(f"{name}: exclude {tuple(exclude.shape)} is not [{nq}]")
+    ins = [queries, index] + ([] if exclude is None else [exclude])
+    outs = []
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError(f"{name}: out must be a pair (scores, ids)")
+        for t, want in zip(out, (torch.float32, torch.int32)):
+            if not torch.is_tensor(t) or t.dtype != want:
+                raise TypeError(f"{name}: out must be (fp32 scores, int32 ids)")
+            if tuple(t.shape) != (nq, k):
+                raise ValueError(f"{name}: an out tensor is {tuple(t.shape)}, not [{nq}, {k}]")
+        outs = list(out)
+        if _shares_memory(outs[0], outs[1]) or any(_shares_memory(o, t) for o in outs
+                                                   for t in ins):
+            raise ValueError(f"{name}: out shares memory with an input or with itself")
+    for t in ins + outs:
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: an operand is not contiguous (never copied here)")
+        if not t.is_cuda or t.device != index.device:
+            raise ValueError(f"{name}: an operand is on {t.device}; the kernel runs on the GPU, "
+                             f"all operands on one device")
+    if queries.data_ptr() % 16 or index.data_ptr() % 16:
+        raise ValueError(f"{name}: queries and index must be 16-byte aligned")
+    if exclude is not None and bool(((exclude < -1) | (exclude >= N)).any()):
+        raise ValueError(f"{name}: exclude has an entry outside [-1, {N})")
+    need = int(L.lib().mmdx_topk_similar_workspace_size(N, d, nq, k))
+    if need <= 0:
+        raise ValueError(f"{name}: unsupported shape N = {N}, d = {d}, nq = {nq}, k = {k}")
+    ws = L.workspace(need, index.device)
+    if out is None:
+        outs = [torch.empty((nq, k), dtype=torch.float32, device=index.device),
+                torch.empty((nq, k), dtype=torch.int32, device=index.device)]
+    call("mmdx_topk_similar", stream(), dt, ptr(queries), ptr(index), N, d, nq, k, ptr(exclude),
+         ptr(outs[0]), ptr(outs[1]), ptr(ws), need)
+    return outs[0], outs[1]

@@ -154,7 +154,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
                    augment=None, criterion=None, uncertain=None, calibrate=None, bootstrap=0,
-                   clahe=None):
+                   clahe=None, case_index=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -194,7 +194,16 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     equalises the decoded pixels on the GPU before the transform (mmdx.clahe).  It is part of
     the model's input definition, not an augmentation: it applies to the image tower's training
     batches (before `augment`), to the fusion phase's encode and to the validation batches
-    alike, and its config() is stored under artifacts["clahe"], where inference() finds it."""
+    alike, and its config() is stored under artifacts["clahe"], where inference() finds it.
+
+    case_index (default None = the run, the files and the keys are what they were) = True, with
+    save=True, builds an mmdx.retrieval.CaseIndex from the fusion rows' z_fuse after the fusion
+    phase (keys = their image_url, the run's clahe config, the three modules' fingerprint),
+    saves it as case_index.pt next to model_bundle.pt and returns out["case_index"] = {"path",
+    "n", "self_agreement": self_agreement(min(5, n - 1))} (self_agreement None for one row)."""
+    if case_index not in (None, False, True):
+        raise TypeError(f"training_tests: case_index must be None or a bool, got "
+                        f"{type(case_index).__name__}")
     if clahe is not None:
         from .clahe import Clahe
         if not isinstance(clahe, Clahe):
@@ -446,5 +455,20 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             t5_tokenizer=t5_tok, save_t5_weights=False, hf_model_name="t5-small")
         log("model version in registry:", rm.version)
         out["registry_version"] = rm.version
+        if case_index:
+            from .retrieval import CaseIndex, model_fingerprint
+            with torch.no_grad():
+                z_fuse = fusion_model(z_img=z_img, z_txt=z_txt, report_labels=None)["z_fuse"]
+            idx = CaseIndex.from_vectors(
+                z_fuse, y_multi, rows["image_url"].astype(str).tolist(),
+                class_names=list(DISEASES),
+                fingerprint=model_fingerprint(image_encoder, text_encoder, fusion_model),
+                clahe=clahe.config() if clahe is not None else None)
+            mdir = os.environ.get("MMDX_MODEL_DIR") or str(REG.registry_root().parent / "model")
+            path = idx.save(os.path.join(mdir, "case_index.pt"))
+            n_idx = len(idx)
+            out["case_index"] = {"path": path, "n": n_idx, "self_agreement":
+                                 idx.self_agreement(min(5, n_idx - 1)) if n_idx > 1 else None}
+            log(f"case index: {n_idx} rows -> {path}")
     out["models"] = (image_encoder, text_encoder, fusion_model)
     return out
