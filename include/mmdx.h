@@ -1063,6 +1063,51 @@ int mmdx_clahe_apply(const uint8_t* pixels, size_t pixel_bytes,
                      const uint8_t* luts, size_t lut_bytes, uint8_t* out, size_t out_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------- 16-bit windowing
+ * Grey-level windowing of 16-bit single-channel images to 8 bits (mmdx/window.py states it and
+ * its numpy `reference` is the definition these kernels equal byte for byte).  pixels: the
+ * images' uint16 pixels, every image starting at a 16-byte boundary and padded to one
+ * (src_off and the buffer's size are multiples of 16; the padding is read, never used).
+ * out: the (H, W, 1) uint8 images packed back to back, the buffer mmdx_clahe_* and
+ * mmdx_image_preprocess take.  One descriptor per image.
+ *
+ * mmdx_window_levels (mode 0 descriptors only): per image a 65536-bin uint32 histogram in
+ * `workspace` (integer atomics), then lo = the k_lo-th and hi = the k_hi-th order statistic
+ * (0-based) of its pixels, hi = lo + 1 when they are equal, written to
+ * levels[4 b + {0, 1, 2, 3}] = lo, hi, the bits of 255.0f / float(hi - lo), 0 on the device.
+ * workspace: mmdx_window_workspace_size(B) bytes (0 for a B outside the limits), 16-byte
+ * aligned, ALL ZERO on entry; it is all zero again when the call's work on `stream` is done,
+ * so a second call needs no reset.
+ *
+ * mmdx_window_apply: y = clamp(rint((float(v) - lo) * scale), 0, 255), one exact fp32
+ * subtraction, one fp32 multiply, rounding half to even; 255 - y when invert.  Mode 0 takes lo
+ * and scale from `levels` (the array mmdx_window_levels wrote), mode 1 from the descriptor;
+ * levels may be NULL when every descriptor has mode 1.
+ *
+ * Both take the descriptor table twice, as the CLAHE entries do: descs_host (HOST memory) is
+ * validated in full before any launch and sizes the grid; descs_dev is the same table in
+ * DEVICE memory.  Limits: 1 <= w, h <= 65535; w * h <= 2^30; B <= 65535; mode 0:
+ * 0 <= k_lo <= k_hi < w * h; mode 1: lo, hi multiples of 0.5 with
+ * -65536 <= lo < hi <= 131072 and scale == 255.0f / (hi - lo); sources and outputs in
+ * descriptor order without overlap; out must not overlap pixels.  Integer atomics only, so the
+ * result is bit-reproducible, and an image's result does not depend on the rest of the batch. */
+typedef struct {
+  long src_off, dst_off; /* byte offsets: uint16 source (multiple of 16), uint8 destination */
+  int w, h;              /* width, height */
+  int mode;              /* 0 = percentile (ranks below), 1 = fixed (lo, hi, scale below) */
+  int invert;            /* 0 / 1: write 255 - y */
+  int k_lo, k_hi;        /* mode 0: 0-based ranks of the two order statistics */
+  float lo, hi, scale;   /* mode 1: the window and 255.0f / (hi - lo) */
+} mmdx_window_desc;
+size_t mmdx_window_desc_size(void); /* sizeof(mmdx_window_desc): binding layout check */
+size_t mmdx_window_workspace_size(int B);
+int mmdx_window_levels(const uint16_t* pixels, size_t pixel_bytes,
+                       const mmdx_window_desc* descs_host, const mmdx_window_desc* descs_dev,
+                       int B, void* workspace, size_t workspace_bytes, int* levels, void* stream);
+int mmdx_window_apply(const uint16_t* pixels, size_t pixel_bytes,
+                      const mmdx_window_desc* descs_host, const mmdx_window_desc* descs_dev, int B,
+                      const int* levels, uint8_t* out, size_t out_bytes, void* stream);
+
 /* ---------------------------------------------------------------- similar-case retrieval
  * Exact top-k inner-product search (mmdx/retrieval.py: reference_search is the definition).
  * index [N][d] row-major, queries [nq][d], both `dtype` (fp32, bf16 or fp16), 16-byte aligned.

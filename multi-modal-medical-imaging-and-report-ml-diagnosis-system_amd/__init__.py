@@ -14,6 +14,7 @@ from .amp import GradScaler  # noqa: F401
 from .preprocess import preprocess_batch  # noqa: F401
 from .augment import Augment  # noqa: F401
 from .clahe import Clahe  # noqa: F401
+from .window import Window  # noqa: F401
 from .losses import DiseaseLoss  # noqa: F401
 from . import bootstrap  # noqa: F401
 from . import retrieval  # noqa: F401

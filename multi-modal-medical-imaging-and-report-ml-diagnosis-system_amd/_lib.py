@@ -237,6 +237,10 @@ SIGNATURES = {
     "mmdx_clahe_desc_size": (sz, []),
     "mmdx_clahe_luts": (i32, [vp, sz, vp, vp, i32, vp, sz, vp]),
     "mmdx_clahe_apply": (i32, [vp, sz, vp, vp, i32, vp, sz, vp, sz, vp]),
+    "mmdx_window_desc_size": (sz, []),
+    "mmdx_window_workspace_size": (sz, [i32]),
+    "mmdx_window_levels": (i32, [vp, sz, vp, vp, i32, vp, sz, vp, vp]),
+    "mmdx_window_apply": (i32, [vp, sz, vp, vp, i32, vp, vp, sz, vp]),
     "mmdx_topk_rows_per_block": (i32, []),
     "mmdx_topk_similar_workspace_size": (sz, [i64, i32, i32, i32]),
     "mmdx_topk_similar": (i32, [vp, i32, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, sz]),

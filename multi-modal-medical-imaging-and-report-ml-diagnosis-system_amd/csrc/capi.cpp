@@ -52,6 +52,8 @@ static Knobs read_knobs() {
   k.attn_bwd_nw = (int)env_long("MMDX_ATTN_BWD_NW", 0);
   k.lstm_bwd_probe = env_long("MMDX_LSTM_BWD_PROBE", 0) != 0;
   k.bn_bwd_pair = env_long("MMDX_BN_BWD_PAIR", 1) != 0;
+  const long ws = env_long("MMDX_WINDOW_SPAN", 0);
+  k.window_span = ws >= 1 && ws <= 8 ? (int)ws : 0;
   return k;
 }
 

@@ -46,6 +46,7 @@ struct Knobs {
   int attn_bwd_nw;        // MMDX_ATTN_BWD_NW: raw value (0 = unset)
   bool lstm_bwd_probe;    // MMDX_LSTM_BWD_PROBE: lab phase stamps (tools/lab/lstm_probe.py)
   bool bn_bwd_pair;       // MMDX_BN_BWD_PAIR (default on): mmdx_bn_bwd_pair_enabled()
+  int window_span;        // MMDX_WINDOW_SPAN: 1 .. 8 chunks per histogram block (0 = by size)
 };
 const Knobs& knobs();
 

@@ -202,10 +202,13 @@ class LocalCXRBatches:
     label values bit for bit.  `clahe` (an mmdx.Clahe) equalises the decoded full-resolution
     pixels on the GPU before the transform, hence before `augment`; it is part of the model's
     input definition, so training and validation loaders of one model carry the same setting.
-    None yields the unequalised batches, bit for bit what they were without the argument."""
+    None yields the unequalised batches, bit for bit what they were without the argument.
+    `window` (an mmdx.Window) is the grey-level window of a 16-bit dataset (16-bit PNGs): the
+    decoded I;16 images are windowed to 8 bits on the GPU before `clahe` and the transform; like
+    `clahe` it is part of the model's input definition.  None (default) takes 8-bit images."""
 
     def __init__(self, df, image_root, batch_size=32, shuffle=True, seed=0, drop_last=False,
-                 device=None, augment=None, uncertain=None, clahe=None):
+                 device=None, augment=None, uncertain=None, clahe=None, window=None):
         self.keys, self.labels = construct_input_label_pairs_for_image_encoder_dataset(df)
         if uncertain is not None and self.labels:
             self.labels = list(apply_uncertain(np.stack(self.labels), uncertain))
@@ -223,6 +226,12 @@ class LocalCXRBatches:
                 raise TypeError(f"clahe must be an mmdx.Clahe or None, got "
                                 f"{type(clahe).__name__}")
         self.clahe = clahe
+        if window is not None:
+            from .window import Window
+            if not isinstance(window, Window):
+                raise TypeError(f"window must be an mmdx.Window or None, got "
+                                f"{type(window).__name__}")
+        self.window = window
 
     def __len__(self):
         n = len(self.keys)
@@ -243,7 +252,10 @@ class LocalCXRBatches:
             if self.drop_last and len(idx) < self.batch_size:
                 break
             imgs = [open_image(self.image_root, self.keys[i]) for i in idx]
-            x = preprocess_batch(imgs, dev, clahe=self.clahe)
+            if self.window is not None:
+                x = preprocess_batch(imgs, dev, clahe=self.clahe, window=self.window)
+            else:
+                x = preprocess_batch(imgs, dev, clahe=self.clahe)
             if self.augment is not None:
                 x = self.augment(x)
             y = torch.from_numpy(np.stack([self.labels[i] for i in idx])).to(dev)

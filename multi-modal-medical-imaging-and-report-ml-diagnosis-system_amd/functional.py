@@ -19,6 +19,7 @@ __all__ = [
     "gemm", "cast", "linear", "fusion_linear", "layer_norm", "dropout", "bce_with_logits",
     "masked_mean", "embed_mean", "auroc_counts", "confusion_grid", "cam_raw", "cam_resize",
     "augment_affine", "disease_loss", "calib_fit", "reliability_bins", "clahe",
+    "window16", "window_passes",
     "attention_relevance", "rollout_step", "token_relevance_step",
 ]
 
@@ -1100,6 +1101,93 @@ def clahe(images, clip_limit=2.0, tiles=(8, 8), return_luts=False, device=None):
         t = luts[lo:lo + c * ty * tx * 256].view(c, ty, tx, 256)
         tabs.append(t[0] if len(shp) == 2 else t)
     return (res, tabs) if return_luts else res
+
+
+# ----------------------------------------------------------------------------- 16-bit windowing
+_WINDOW_WS: dict = {}
+
+
+def _window_workspace(B, device):
+    """The histogram workspace of mmdx_window_levels for (device, current stream): allocated
+    zeroed once (a memset on the stream) and left zero by every call, so it is reused without
+    a reset; it grows when a larger batch comes."""
+    need = call("mmdx_window_workspace_size", B)
+    if need == 0:
+        raise ValueError(f"window: a batch of {B} images is outside the limits")
+    key = (device.index, stream())
+    ws = _WINDOW_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _WINDOW_WS[key] = torch.zeros(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def window_passes(px16, descs):
+    """The window launches (mmdx_window_levels in percentile mode, then mmdx_window_apply) on
+    the packed device buffer `px16` of 16-bit pixels that the table `descs` of window.plan
+    describes (a flat uint8 tensor of its bytes, or a flat int16 / uint16 one).  Returns (the
+    packed uint8 buffer in the (H, W, 1) layout of clahe.plan and preprocess.plan_batch, the
+    [B, 2] int32 windows (lo, hi) on the device; None in fixed mode, where the window is the
+    setting's).  The C entries validate the table against the buffers before they launch;
+    nothing here copies pixels or synchronises."""
+    from . import window as W
+    if px16.dim() != 1 or not px16.is_contiguous() or px16.element_size() not in (1, 2) or \
+            px16.is_floating_point():
+        raise ValueError("window: the pixel buffer must be a flat contiguous tensor of the "
+                         "16-bit pixels (uint8 bytes, int16 or uint16)")
+    L.require_device(px16)
+    if call("mmdx_window_desc_size") != W.DESC.itemsize:
+        raise RuntimeError("mmdx_window_desc layout differs between the library and window.DESC")
+    B, src_bytes = len(descs), px16.numel() * px16.element_size()
+    out_bytes = int(descs["dst_off"][-1]) + int(descs["w"][-1]) * int(descs["h"][-1])
+    percentile = bool((descs["mode"] == 0).all())
+    with torch.cuda.device(px16.device):
+        d_desc = torch.from_numpy(descs.view(np.uint8).copy()).to(px16.device, non_blocking=True)
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=px16.device)
+        levels = None
+        if percentile:
+            ws = _window_workspace(B, px16.device)
+            levels = torch.empty((B, 4), dtype=torch.int32, device=px16.device)
+            call("mmdx_window_levels", ptr(px16), src_bytes, descs.ctypes.data, ptr(d_desc), B,
+                 ptr(ws), ws.numel(), ptr(levels), stream())
+        call("mmdx_window_apply", ptr(px16), src_bytes, descs.ctypes.data, ptr(d_desc), B,
+             ptr(levels), ptr(out), out_bytes, stream())
+    return out, (levels[:, :2] if percentile else None)
+
+
+def window16(images, window, return_window=False, device=None):
+    """Windowing of 16-bit images to 8 bits (mmdx.window: the definition and its numpy
+    `reference`, which this equals byte for byte) for a list of HxW / HxWx1 uint16 arrays or
+    PIL I;16 images of any sizes, in three launches for the whole list (one in fixed mode).
+    Returns a list of device uint8 tensors [H, W], and with return_window also the list of
+    (lo, hi) the images were mapped with (read back from the device in percentile mode).
+    Limits (TypeError / ValueError before any launch): uint16 only, one channel, sides in
+    [1, 65535], H * W <= 2^30, and those of mmdx.Window."""
+    from . import window as W
+    if not isinstance(window, W.Window):
+        raise TypeError(f"window must be an mmdx.Window, got {type(window).__name__}")
+    if isinstance(images, (np.ndarray, torch.Tensor)) or hasattr(images, "mode"):
+        raise TypeError("window16 takes a list of images")
+    planes = [W.as_plane(im) for im in images]
+    descs, src_bytes, _ = W.plan(planes, window)   # every limit, before any upload
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("functional.window16 runs on the GPU (HIP); mmdx.window.reference "
+                           "is the host statement")
+    host = np.zeros(src_bytes, dtype=np.uint8)
+    W.pack(planes, descs, host)
+    with torch.cuda.device(device):
+        out, levels = window_passes(torch.from_numpy(host).to(device), descs)
+    res = []
+    for d, a in zip(descs, planes):
+        o = int(d["dst_off"])
+        res.append(out[o:o + a.size].view(a.shape))
+    if not return_window:
+        return res
+    if levels is None:
+        return res, [(window.lo, window.hi)] * len(planes)
+    return res, [(int(lo), int(hi)) for lo, hi in levels.cpu().tolist()]
 
 
 # ----------------------------------------------------------------------------- retrieval

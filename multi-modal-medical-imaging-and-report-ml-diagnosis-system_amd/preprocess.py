@@ -159,14 +159,26 @@ def plan_batch(arrays):
     return descs, coef.astype(np.int32), max(temp_off, 1), max_trows, src_off
 
 
-def preprocess_batch(images, device=None, clahe=None) -> torch.Tensor:
+def preprocess_batch(images, device=None, clahe=None, window=None) -> torch.Tensor:
     """PIL images (L/RGB, any sizes) -> [B, 3, 224, 224] fp32 on the GPU, identical to
     torch.stack([image_transfom_into_tensor(im) for im in images]).
 
     clahe (an mmdx.Clahe, default None = the two launches and the bits above) equalises the
     full-resolution pixels first: two more launches (mmdx.clahe) on the uploaded pixel buffer,
     no further host-device copy of pixels and no further synchronisation.  The result is that
-    of transforming mmdx.clahe.reference(im, ...) of every image."""
+    of transforming mmdx.clahe.reference(im, ...) of every image.
+
+    window (an mmdx.Window, default None = 8-bit images only, as above) takes 16-bit
+    single-channel images instead (uint16 HxW / HxWx1 arrays, PIL I;16): their pixels are
+    uploaded once through the same pinned staging, windowed to 8 bits on the GPU (mmdx.window,
+    up to three more launches), then equalised if `clahe` is given, then transformed.  The
+    result is that of transforming mmdx.window.reference(im, window) of every image.  Every
+    image of the batch must be 16-bit: a TypeError names the first that is not."""
+    if window is not None:
+        from . import window as W
+        if not isinstance(window, W.Window):
+            raise TypeError(f"window must be an mmdx.Window or None, got "
+                            f"{type(window).__name__}")
     if clahe is not None:
         from . import clahe as K
         if not isinstance(clahe, K.Clahe):
@@ -177,24 +189,46 @@ def preprocess_batch(images, device=None, clahe=None) -> torch.Tensor:
     if device.type != "cuda":
         raise RuntimeError("mmdx preprocessing runs on the GPU (HIP); there is no CPU path "
                            "here — use training_pipeline.image_transfom_into_tensor on CPU")
-    arrays = [_as_array(im) for im in images]
+    if window is not None:
+        planes = []
+        for i, im in enumerate(images):
+            try:
+                planes.append(W.as_plane(im))
+            except TypeError as e:
+                raise TypeError(f"preprocess_batch(window=...): image {i} is not a 16-bit "
+                                f"single-channel image ({e})") from None
+        if not planes:
+            raise ValueError("empty batch")
+        w_descs, w_bytes, _ = W.plan(planes, window)
+        # stand-ins with the shape and size of the windowed (H, W, 1) uint8 images: the plans
+        # below read nothing else
+        arrays = [np.broadcast_to(np.uint8(0), a.shape + (1,)) for a in planes]
+    else:
+        arrays = [_as_array(im) for im in images]
     if not arrays:
         raise ValueError("empty batch")
     descs, coef, temp_bytes, max_trows, total = plan_batch(arrays)
     if clahe is not None:  # its limits raise here, before anything is uploaded
         cl_descs, _, cl_lut_bytes = K.plan(arrays, clahe)
-    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-    hv = host.numpy()
-    off = 0
-    for a in arrays:
-        hv[off:off + a.nbytes] = a.reshape(-1)
-        off += a.nbytes
+    if window is not None:
+        host = torch.empty(w_bytes, dtype=torch.uint8, pin_memory=True)
+        W.pack(planes, w_descs, host.numpy())
+    else:
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        off = 0
+        for a in arrays:
+            hv[off:off + a.nbytes] = a.reshape(-1)
+            off += a.nbytes
     px = host.to(device, non_blocking=True)
     d_desc = torch.from_numpy(descs.view(np.uint8).copy()).to(device, non_blocking=True)
     d_coef = torch.from_numpy(coef).to(device, non_blocking=True)
     temp = torch.empty(temp_bytes, dtype=torch.uint8, device=device)
     out = torch.empty((len(arrays), 3, CROP, CROP), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
+        if window is not None:  # 16-bit buffer -> the packed uint8 layout of `descs`
+            from .functional import window_passes
+            px, _ = window_passes(px, w_descs)
         if clahe is not None:  # same packed layout, same descriptors for the transform
             from .functional import clahe_passes
             px, _ = clahe_passes(px, cl_descs, cl_lut_bytes)

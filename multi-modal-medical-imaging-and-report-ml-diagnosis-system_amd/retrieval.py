@@ -117,7 +117,9 @@ def _check_rows(vectors, labels, keys, d=None, C=None):
 
 class CaseIndex:
     """vectors [N, d] (index dtype, on the device), labels [N, C] fp32 (NaN = no label), keys
-    (list of str) and meta {metric, dtype, d, n_disease, class_names, fingerprint, clahe}."""
+    (list of str) and meta {metric, dtype, d, n_disease, class_names, fingerprint, clahe} plus
+    "window" when the index was built from windowed 16-bit images (an index without the key
+    was not: meta.get("window") is None)."""
 
     def __init__(self, vectors, labels, keys, meta):
         self._vec, self._lab, self._n = vectors, labels, vectors.shape[0]
@@ -138,7 +140,7 @@ class CaseIndex:
 
     @classmethod
     def from_vectors(cls, vectors, labels, keys, metric="cosine", dtype=torch.float16,
-                     class_names=None, fingerprint=None, clahe=None):
+                     class_names=None, fingerprint=None, clahe=None, window=None):
         """Index the rows of `vectors` [N, d] (any float dtype; they are taken to fp32 first).
         "cosine" divides each row by its fp32 L2 norm, then rounds ONCE to `dtype` (an all-zero
         row stays zero); "ip" only rounds.  A non-finite input is a ValueError."""
@@ -160,6 +162,8 @@ class CaseIndex:
         meta = {"metric": metric, "dtype": str(dtype).replace("torch.", ""), "d": int(d),
                 "n_disease": int(C), "class_names": names, "fingerprint": fingerprint,
                 "clahe": clahe}
+        if window is not None:
+            meta["window"] = window
         return cls(vec, lab, keys, meta)
 
     @classmethod
@@ -170,7 +174,7 @@ class CaseIndex:
         host sync per batch) and index z_fuse with the labels.  `keys` defaults to batches.keys
         when the loader has them and does not shuffle; a shuffling loader without explicit keys
         is a ValueError (its order is not the order of its keys).  Stores the models'
-        fingerprint and the loader's CLAHE config."""
+        fingerprint and the loader's CLAHE and window configs."""
         from .metrics import _append_rows
         from .training_pipeline import tokenize_patient_details
         if keys is None:
@@ -216,13 +220,15 @@ class CaseIndex:
         if n == 0:
             raise ValueError("CaseIndex.build: no rows")
         cl = getattr(batches, "clahe", None)
+        wn = getattr(batches, "window", None)
         keys = list(keys)
         if getattr(batches, "drop_last", False):
             keys = keys[:n]
         return cls.from_vectors(zbuf[:n], ybuf[:n], keys,
                                 metric=metric, dtype=dtype, class_names=class_names,
                                 fingerprint=model_fingerprint(*modules),
-                                clahe=cl.config() if cl is not None else None)
+                                clahe=cl.config() if cl is not None else None,
+                                window=wn.config() if wn is not None else None)
 
     def add(self, vectors, labels, keys):
         """Append rows (normalised and rounded as from_vectors does), doubling the capacity

@@ -86,15 +86,18 @@ def t5_tokenizer():
     return _HashT5Tokenizer()
 
 
-def _open_row_image(url):
+def _open_row_image(url, raw=False):
     """An image_url of the feature group -> PIL RGB image: s3:// URLs through the S3 mirror
-    (TP:957-960), other strings as local paths (relative to MMDX_IMAGE_ROOT)."""
+    (TP:957-960), other strings as local paths (relative to MMDX_IMAGE_ROOT).  raw: the image
+    as decoded, without the conversion (a 16-bit image on its way to preprocess_batch(window=))."""
     from PIL import Image
     from .data import open_image
     if url.startswith("s3://"):
         b, k = REG.parse_s3_url(url)
-        return Image.open(io.BytesIO(REG.get_image_from_s3(b, k))).convert("RGB")
-    return open_image(os.environ.get("MMDX_IMAGE_ROOT", ""), url).convert("RGB")
+        img = Image.open(io.BytesIO(REG.get_image_from_s3(b, k)))
+    else:
+        img = open_image(os.environ.get("MMDX_IMAGE_ROOT", ""), url)
+    return img if raw else img.convert("RGB")
 
 
 def _image_root_for(df):
@@ -154,7 +157,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                    text_model="bert-base-uncased", gen_kwargs=None, save=True,
                    model_name="fusion_model_T5", device=None, verbose=True, val_rows=0,
                    augment=None, criterion=None, uncertain=None, calibrate=None, bootstrap=0,
-                   clahe=None, case_index=None):
+                   clahe=None, case_index=None, window=None):
     """TP:808-1127 on mmdx (see the module docstring).  Returns a dict of what the reference
     prints: tensor shapes, per-step losses and the generated ids / disease vectors.
 
@@ -196,6 +199,13 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     batches (before `augment`), to the fusion phase's encode and to the validation batches
     alike, and its config() is stored under artifacts["clahe"], where inference() finds it.
 
+    window (an mmdx.Window, default None = 8-bit images, the bundle and the batches are what
+    they were) is the grey-level window of a 16-bit dataset: the decoded 16-bit images reach
+    preprocess_batch unconverted and are windowed to 8 bits on the GPU (mmdx.window) before
+    `clahe` and the transform, in the image tower's training batches, the fusion phase's encode
+    and the validation batches alike; its config() is stored under artifacts["window"], where
+    inference() finds it, and in the case index's meta.
+
     case_index (default None = the run, the files and the keys are what they were) = True, with
     save=True, builds an mmdx.retrieval.CaseIndex from the fusion rows' z_fuse after the fusion
     phase (keys = their image_url, the run's clahe config, the three modules' fingerprint),
@@ -210,6 +220,12 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             raise TypeError(f"training_tests: clahe must be an mmdx.Clahe or None, got "
                             f"{type(clahe).__name__}")
         clahe.check()
+    if window is not None:
+        from .window import Window
+        if not isinstance(window, Window):
+            raise TypeError(f"training_tests: window must be an mmdx.Window or None, got "
+                            f"{type(window).__name__}")
+        window.check()
     from .bootstrap import check_args
     bootstrap = check_args(bootstrap, who="training_tests")[0]
     if bootstrap and val_rows <= 0:
@@ -237,14 +253,18 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
     out["n_rows"] = len(df)
 
     log("----------IMAGE ENCODER: IMAGE TRANSFORM TEST SINGLE IMAGE----------")
-    pil = _open_row_image(df["image_url"].iloc[0])
+    if window is not None:
+        pil = Image.fromarray(window(_open_row_image(df["image_url"].iloc[0], raw=True)))
+    else:
+        pil = _open_row_image(df["image_url"].iloc[0])
     t = TP.image_transfom_into_tensor(pil)
     log(t.shape, t.dtype)
     out["transform_shape"] = tuple(t.shape)
 
     log("----------IMAGE ENCODER: DATASET / BATCHES----------")
     batches = LocalCXRBatches(df, _image_root_for(df), batch_size=batch_size, shuffle=True,
-                              device=dev, augment=augment, uncertain=uncertain, clahe=clahe)
+                              device=dev, augment=augment, uncertain=uncertain, clahe=clahe,
+                              window=window)
     imgs, _, y = next(iter(batches))
     log(f"batch img input shape: {tuple(imgs.shape)}, labels {tuple(y.shape)}")
 
@@ -321,7 +341,12 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
         val_df = val_df.reset_index(drop=True)
     rows = rows.reset_index(drop=True)
     from .preprocess import preprocess_batch
-    imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev, clahe=clahe)
+    if window is not None:
+        imgs = preprocess_batch([_open_row_image(u, raw=True) for u in rows["image_url"]], dev,
+                                clahe=clahe, window=window)
+    else:
+        imgs = preprocess_batch([_open_row_image(u) for u in rows["image_url"]], dev,
+                                clahe=clahe)
     y_multi = torch.tensor(apply_uncertain(
         np.stack([np.asarray(v, dtype=np.float32)
                   for v in rows["disease_classification_vector"]]), uncertain),
@@ -407,7 +432,7 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                        LocalCXRBatches(val_df, _image_root_for(val_df), batch_size=batch_size,
                                        shuffle=False, device=dev,
                                        uncertain=None if uncertain is None else "ignore",
-                                       clahe=clahe),
+                                       clahe=clahe, window=window),
                        generate=True, gen_kwargs=gen, report_labels=val_labels,
                        criterion=None if plain_loss else criterion, calibrate=calibrate,
                        bootstrap=bootstrap)
@@ -446,6 +471,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
             artifacts["calibration"] = calibration
         if clahe is not None:
             artifacts["clahe"] = clahe.config()
+        if window is not None:
+            artifacts["window"] = window.config()
         rm = save_model_to_hopsworks_model_registry(
             fusion_model=fusion_model, text_encoder=text_encoder, image_encoder=image_encoder,
             model_name=model_name, description="CXR fusion: CNN+Text -> MLP; multi-label "
@@ -463,7 +490,8 @@ def training_tests(num_steps=300, b_fusion=10, batch_size=32, image_backbone="re
                 z_fuse, y_multi, rows["image_url"].astype(str).tolist(),
                 class_names=list(DISEASES),
                 fingerprint=model_fingerprint(image_encoder, text_encoder, fusion_model),
-                clahe=clahe.config() if clahe is not None else None)
+                clahe=clahe.config() if clahe is not None else None,
+                window=window.config() if window is not None else None)
             mdir = os.environ.get("MMDX_MODEL_DIR") or str(REG.registry_root().parent / "model")
             path = idx.save(os.path.join(mdir, "case_index.pt"))
             n_idx = len(idx)
